@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: ray-samples/s per optimiser step of the LONER sigma-field path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 A "step" is one full optimiser step of the reference's step loop (src/mapping/optimizer.py:354-475)
 on one ray batch: OGM sampling -> hash-grid encode -> sigma MLP -> compositing -> LiDAR loss ->
@@ -16,12 +16,17 @@ Multi-GPU (torchrun): one process per GPU, each rank optimises its own 8192-ray 
 batch of 8192*N rays (weak scaling) and the sigma gradients (7.4 M params, 29.7 MB fp32) plus the
 loss normaliser are all-reduced over RCCL once per step.
 
-Rank 0 prints one JSON line (contract in the task statement), including
+A plain run sets up, warms up, times the K steps and prints rank 0's JSON line: metric, value, unit,
+ms_per_step (one timed step), dtype, the workload's description and the last step's loss.  ``--dump-outputs DIR``
+also writes what the last timed step computed (DIR/<name>.npy, dump_outputs below; same arguments, same inputs).
+``--full`` adds everything that takes steps or runs of its own: the from-init timing before the pre-training
+(from_init), PROF_STEPS untimed steps with per-stage HIP events (stage_ms, ert, the live fractions), and
   roofline      hash-grid backward stage (the dominant stage) against HBM peak, algorithmic bytes
                 1024 B/sample, duration from HIP events on the launch stream
   mfma          the sigma MLP (12,672 FLOP/sample) over the field stage against the dense fp16 MFMA
                 peak, plus the PMC MFMA-busy fraction of its kernels from profiles/*_mfma_<cfg>.json
-  cpu_baseline  the pure-PyTorch CPU restatement (oracle/torch_step.py) on a bounded sample, host threads
+  cpu_baseline  the pure-PyTorch CPU restatement (oracle/torch_step.py) on a bounded sample, host threads, and
+                the rendered-depth check against the oracle (``--no-cpu-baseline`` leaves both out)
 """
 import argparse
 import json
@@ -79,7 +84,15 @@ def parse():
     ap.add_argument("--joint-poses", action="store_true",
                     help="the timed window optimises the keyframe poses with the map (the joint config of the "
                          "reference's default mapper schedule, cfg/defaults.yaml:93-97; keyframe 0 anchored)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-stage HIP-event steps after the "
+                         "timed ones (stage_ms, roofline, backward_stage, mfma, ert, live fractions), the from-init "
+                         "timing before the pre-training (from_init), the CPU baseline and the rendered-depth check "
+                         "against the oracle (cpu_baseline; --no-cpu-baseline leaves those two out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned and updated as "
+                         "DIR/<name>.npy (float32; at most 64 MB in all, a fixed seeded sample of a larger array)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline entry")
     ap.add_argument("--cpu-rays", type=int, default=512, help="rays per reduced-config CPU-baseline step (x512 samples)")
     ap.add_argument("--cpu-steps", type=int, default=24)
     return ap.parse_args()
@@ -97,6 +110,27 @@ LOSS_PRESETS = {
                    los_lambda_decay_steps=15000, decay_depth_eps=True, depth_eps=3.0, min_depth_eps=0.5,
                    depth_eps_decay_rate=0.95, depth_eps_decay_steps=100, depthloss_lambda=0.005),
 }
+
+
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: the most it writes, over all arrays
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: tensor} as path/<name>.npy in float32 (float64 stays).  The arrays share
+    DUMP_BYTES of payload, smallest first; one that does not fit its share is written as a fixed sample of its
+    flattened elements (sorted indices drawn without replacement by numpy's default_rng(0))."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES - 4096 * len(arrays)  # (the .npy headers)
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        share = left // (len(todo) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def pmc_traffic(cfg_name):
@@ -370,15 +404,9 @@ def bench_render(args):
         run(args.warmup + i, False)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    for i in range(PROF_STEPS):  # per-stage events, untimed
-        run(args.warmup + args.steps + i, True)
-    torch.cuda.synchronize()
-    stage_ms = {k: float(np.mean([v[j].elapsed_time(v[j + 1]) for j in range(0, len(v), 2)])) for k, v in ev.items()}
+    if args.dump_outputs:  # the last timed render: depth, opacity, variance (lnr_field_render's three maps), colour
+        dump_outputs(args.dump_outputs, {"depth": outs[0], "opacity": outs[1], "variance": outs[2], "rgb": rgb})
     N = R * S
-    # dominant kernel: the sigma-grid encode, 512 B/sample of gathers (the colour-grid encode skips
-    # the samples of weight exactly 0, so its algorithmic bytes depend on the scene; not used here)
-    enc_ms = stage_ms["encode"]
-    achieved = 512.0 * N / (enc_ms * 1e-3) / 1e9
     line = {"metric": "ray-samples/sec per render (inference)", "value": N * args.steps / elapsed,
             "unit": "ray-samples/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -386,12 +414,24 @@ def bench_render(args):
             "data": f"synthetic {kind} LiDAR scene, rays built on the GPU per render; random-init sigma field",
             "config": {"workload": f"C3: {R} rays x {S} samples, peak rendering, sigma head (L=16 T=2^18 + 64-wide "
                                    f"MLP) + colour head (SH4 + L=16 T=2^19 + 48->64x4->3 MLP)",
-                       "rays": R, "samples_per_ray": S, "parallelism": "single"},
+                       "rays": R, "samples_per_ray": S, "parallelism": "single"}}
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
+    for i in range(PROF_STEPS):  # per-stage events, untimed
+        run(args.warmup + args.steps + i, True)
+    torch.cuda.synchronize()
+    stage_ms = {k: float(np.mean([v[j].elapsed_time(v[j + 1]) for j in range(0, len(v), 2)])) for k, v in ev.items()}
+    # dominant kernel: the sigma-grid encode, 512 B/sample of gathers (the colour-grid encode skips
+    # the samples of weight exactly 0, so its algorithmic bytes depend on the scene; not used here)
+    enc_ms = stage_ms["encode"]
+    achieved = 512.0 * N / (enc_ms * 1e-3) / 1e9
+    line.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                          "kernel": "sigma hash-grid forward (k_hashgrid_fwd), 512 B/sample of gathers",
                          "algorithmic_bytes_per_launch": 512 * N, "ms_per_launch": enc_ms},
-            "stage_ms": stage_ms}
+            "stage_ms": stage_ms})
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_render(kind, 4096, S)
         line["cpu_baseline"]["rendered_depth_vs_oracle"] = rendered_depth_vs_oracle(state, window, 256, S)
@@ -489,6 +529,10 @@ def bench_camera(args):
             n_tot += run(args.warmup + i, False)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:  # the last timed iteration: its colour map and loss, the colour parameters after it
+            dumped.update(rgb=eng.rgb.clone(), loss=eng.loss.clone(), colour_params=eng.color.params.clone())
+        if not args.full:
+            return elapsed, n_tot, None, None
         for i in range(PROF_STEPS):  # whole-iteration events, untimed
             run(args.warmup + args.steps + i, True)
         # one extra profiled iteration split by stage (events between the engine's launches)
@@ -498,14 +542,16 @@ def bench_camera(args):
 
     field = args.field or "trained"
     from_init, pre = None, None
+    dumped = {}
     if field == "trained":
         # the driver's camera phase runs on a sigma field its LiDAR phase has trained: most samples have weight 0
         # there (free space, and everything behind the surface), which the colour kernels skip (zero-weight tiles,
         # the live colour encode).  Timed first from init, then after the LiDAR phase's windows (bench.pretrain over
         # the scene's trajectory, C4's shape), with a fresh colour head for the timed iterations.
-        elapsed, n_tot, stage_i, live_i = measure()
-        from_init = {"ms_per_step": elapsed / args.steps * 1e3, "value": n_tot * S / elapsed, "stage_ms": stage_i,
-                     "live_sample_frac": live_i}
+        if args.full:
+            elapsed, n_tot, stage_i, live_i = measure()
+            from_init = {"ms_per_step": elapsed / args.steps * 1e3, "value": n_tot * S / elapsed, "stage_ms": stage_i,
+                         "live_sample_frac": live_i}
         R4 = nkf4 * (rpk4 + spk4)
         leng = S_.StepEngine(state, R4, seed=12345)
         t_pre = time.perf_counter()
@@ -519,9 +565,8 @@ def bench_camera(args):
         torch.cuda.synchronize()
     elapsed, n_tot, stage_ms, live_frac = measure()
     N = n_tot * S
-    bwd_ms = stage_ms["rgb_train"]
-    flop = 2 * 3 * (64 * 48 + 3 * 64 * 64 + 16 * 64) * R * S  # forward (x2: recomputed) + backward GEMMs
-    achieved = flop / (bwd_ms * 1e-3) / 1e12
+    if dumped:
+        dump_outputs(args.dump_outputs, dumped)
     line = {"metric": "ray-samples/sec per colour-head iteration", "value": N / elapsed, "unit": "ray-samples/s",
             "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -534,7 +579,14 @@ def bench_camera(args):
                        "rays": R, "samples_per_ray": S, "parallelism": "single",
                        "field_state": ("trained: the sigma field after %d untimed LiDAR steps (config.pretrain)"
                                        % pre["steps"] if field == "trained" else "from init"),
-                       **({"pretrain": pre} if pre is not None else {})},
+                       **({"pretrain": pre} if pre is not None else {})}}
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
+    bwd_ms = stage_ms["rgb_train"]
+    flop = 2 * 3 * (64 * 48 + 3 * 64 * 64 + 16 * 64) * R * S  # forward (x2: recomputed) + backward GEMMs
+    achieved = flop / (bwd_ms * 1e-3) / 1e12
+    line.update({
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / MFMA_PEAK_TFLOPS, "traffic": None,
                          "kernel": "lnr_rgb_train (colour forward x2 + L1 + MLP backward, MFMA fp16)",
@@ -542,7 +594,7 @@ def bench_camera(args):
             "stage_ms": stage_ms,
             # the share of ray-samples with a non-zero compositing weight (the colour kernels' live samples)
             "live_sample_frac": live_frac,
-            **({"from_init": from_init} if from_init is not None else {})}
+            **({"from_init": from_init} if from_init is not None else {})})
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_camera(96, S, 4)
     print(json.dumps(line), flush=True)
@@ -796,10 +848,14 @@ def main():
         return eng.step(rays, dgt, global_step=i, scale=scale, far_ref=far_ref[i % len(batches)],
                         n_rays_global=r_glob, prof=prof)
 
+    dumped = None  # --dump-outputs: copies taken right after the last timed step (rank 0)
+
     def measure(g0=0):
         """W untimed warm-up steps, then K timed steps (barrier + synchronize on both sides, the max over ranks),
-        then PROF_STEPS untimed steps with per-stage HIP events; returns (seconds, loss, stage ms, the fraction
-        of ray-samples whose dL/dsigma is exactly 0 in the profiled steps)."""
+        then (--full) PROF_STEPS untimed steps with per-stage HIP events; returns (seconds, loss, stage ms, the
+        fraction of ray-samples whose dL/dsigma is exactly 0 in the profiled steps); without --full the last two
+        are None."""
+        nonlocal dumped
         for i in range(args.warmup):
             run(i, g0=g0)
         torch.cuda.synchronize()
@@ -819,6 +875,14 @@ def main():
             dist.all_reduce(e, op=dist.ReduceOp.MAX)
             elapsed = float(e.item())
         loss = out.cpu().numpy()
+        if args.dump_outputs and rank == 0:
+            # what the last timed step returned (the loss record) and updated (the parameters, the OGM), copied
+            # before the profiled steps go on training them
+            eng.finish()
+            dumped = {"loss": out.clone(), "params": state.params[:state.n_params].clone(),
+                      "occupancy_grid": state.occ.clone()}
+        if not args.full:
+            return elapsed, loss, None, None
         # per-stage HIP events in a separate pass after the timed region (recording them costs host time:
         # 47 us per step at C1, where the host issues the step faster than the GPU runs it only without them)
         prof = {}
@@ -874,15 +938,22 @@ def main():
         state.occ.copy_(ck["occ"])
         state.refresh_shadow()
         g0, pre = int(ck["g0"]), dict(json.loads(ck["pre"]), loaded_from=cache)
-    else:
+    elif args.field != "trained" or args.full:  # (the trained field's from-init timing: --full only)
         elapsed, loss, stage_ms, zero_frac = measure()
+    else:
+        # the trained field's history starts with the from-init steps on the bench window: a plain run takes them
+        # untimed (0.1-0.2 s), so that the timed window starts from the same field, and runs at the same speed, as
+        # under --full (without them C2's trained step measured 3 % slower)
+        for i in range(args.warmup + args.steps + PROF_STEPS):
+            run(i)
     if args.field == "trained":
         if not (cache and os.path.exists(cache)):
-            from_init = {"ms_per_step": elapsed / args.steps * 1e3,
-                         "value": world * R * n_samples * args.steps / elapsed,
-                         "loss": float(loss[0]), "dsigma_zero_frac": zero_frac[0], "dead_wave_frac": zero_frac[1],
-                         "ert": zero_frac[2],
-                         "backward": "live" if eng._live else "full", "stage_ms": stage_ms}
+            if args.full:
+                from_init = {"ms_per_step": elapsed / args.steps * 1e3,
+                             "value": world * R * n_samples * args.steps / elapsed,
+                             "loss": float(loss[0]), "dsigma_zero_frac": zero_frac[0], "dead_wave_frac": zero_frac[1],
+                             "ert": zero_frac[2],
+                             "backward": "live" if eng._live else "full", "stage_ms": stage_ms}
             t_pre = time.perf_counter()
             g0, pre = pretrain(eng, state, kind, win_kf, rpk, spk, strat, dev, r_glob,
                                args.warmup + args.steps + PROF_STEPS, args.pretrain_windows, args.pretrain_iters)
@@ -901,34 +972,6 @@ def main():
     N = R * n_samples
     ms = elapsed / args.steps * 1e3
     value = world * N * args.steps / elapsed
-    bwd_ms = stage_ms["grid_bwd"]
-    # one GPU: the table's Adam runs inside the backward's accumulation (lnr_hashgrid_bwd_rays_jac_adam),
-    # so the stage's algorithmic bytes add Adam's 32 B per table parameter
-    fused_adam = eng.fuses_adam(N)
-    # algorithmic work counts the samples that have it: every sample is encoded and goes through the MLP forward
-    # (its sigma decides whether it is dead), but a sample with dL/dsigma = 0 has no scatter-adds and no MLP
-    # backward to do (its contributions are exactly 0; the reference's tcnn path does them all the same)
-    zero_frac, dead_wave_frac, ert = zero_frac
-    n_live = N * (1.0 - zero_frac)
-    bwd_bytes = 1024.0 * n_live + (32.0 * 2 * state.n_entries if fused_adam else 0.0)
-    achieved = bwd_bytes / (bwd_ms * 1e-3) / 1e9
-    traffic, traffic_src = pmc_traffic(args.config)
-    traffic_step, traffic_step_src = pmc_step_traffic(args.config)
-    enc_traffic, enc_traffic_src = pmc_kernel_traffic(args.config, "k_hashgrid_fwd")
-    # the whole step against the HBM bound (SURVEY.md 8(d)): 512 B per ray-sample of gathers, 1024 B per live
-    # ray-sample of scatter-adds, 32 B per parameter (Adam), 52 B per ray
-    n_enc = N * ert.get("encoded_frac", 1.0) if ert["phases"] is not None else N
-    step_bytes = 512.0 * n_enc + 1024.0 * n_live + 32.0 * state.n_params + 52.0 * R
-    busy, busy_src = pmc_mfma(args.config)
-    # (with early ray termination the forward runs in the sigma phases, over the encoded samples)
-    mlp_flop = 4224.0 * n_enc + 8448.0 * n_live
-    mlp_ms = stage_ms["field"] + stage_ms.get("sigma_phases", 0.0)
-    mlp_tflops = mlp_flop / (mlp_ms * 1e-3) / 1e12
-    # the encode launches' time: with early ray termination the stage also holds the sigma phases (timed apart);
-    # the algorithmic gathers are those of the samples encoded (512 B each), as the backward counts live samples
-    enc_ms = stage_ms["encode"] - stage_ms.get("sigma_phases", 0.0)
-    enc_achieved = 512.0 * n_enc / (enc_ms * 1e-3) / 1e9
-    ta, ta_src = pmc_ta_busy(args.config)
     line = {
         # BASELINE.json metric: the rate here, the rendered-depth L1 in cpu_baseline.rendered_depth_vs_oracle
         "metric": "ray-samples/sec per optimizer step; rendered-depth L1 vs reference",
@@ -967,6 +1010,46 @@ def main():
                    "poses": poses_desc,
                    **({"pretrain": pre} if args.field == "trained" else {}),
                    **({"submap_rank0": submap} if submap is not None else {})},
+        "loss": float(loss[0]),
+        # the process group as torch.distributed reports it (None: a single process, no group)
+        "dist": ({"backend": dist.get_backend(), "ranks": dist.get_world_size()} if dist is not None else None),
+    }
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    bwd_ms = stage_ms["grid_bwd"]
+    # one GPU: the table's Adam runs inside the backward's accumulation (lnr_hashgrid_bwd_rays_jac_adam),
+    # so the stage's algorithmic bytes add Adam's 32 B per table parameter
+    fused_adam = eng.fuses_adam(N)
+    # algorithmic work counts the samples that have it: every sample is encoded and goes through the MLP forward
+    # (its sigma decides whether it is dead), but a sample with dL/dsigma = 0 has no scatter-adds and no MLP
+    # backward to do (its contributions are exactly 0; the reference's tcnn path does them all the same)
+    zero_frac, dead_wave_frac, ert = zero_frac
+    n_live = N * (1.0 - zero_frac)
+    bwd_bytes = 1024.0 * n_live + (32.0 * 2 * state.n_entries if fused_adam else 0.0)
+    achieved = bwd_bytes / (bwd_ms * 1e-3) / 1e9
+    traffic, traffic_src = pmc_traffic(args.config)
+    traffic_step, traffic_step_src = pmc_step_traffic(args.config)
+    enc_traffic, enc_traffic_src = pmc_kernel_traffic(args.config, "k_hashgrid_fwd")
+    # the whole step against the HBM bound (SURVEY.md 8(d)): 512 B per ray-sample of gathers, 1024 B per live
+    # ray-sample of scatter-adds, 32 B per parameter (Adam), 52 B per ray
+    n_enc = N * ert.get("encoded_frac", 1.0) if ert["phases"] is not None else N
+    step_bytes = 512.0 * n_enc + 1024.0 * n_live + 32.0 * state.n_params + 52.0 * R
+    busy, busy_src = pmc_mfma(args.config)
+    # (with early ray termination the forward runs in the sigma phases, over the encoded samples)
+    mlp_flop = 4224.0 * n_enc + 8448.0 * n_live
+    mlp_ms = stage_ms["field"] + stage_ms.get("sigma_phases", 0.0)
+    mlp_tflops = mlp_flop / (mlp_ms * 1e-3) / 1e12
+    # the encode launches' time: with early ray termination the stage also holds the sigma phases (timed apart);
+    # the algorithmic gathers are those of the samples encoded (512 B each), as the backward counts live samples
+    enc_ms = stage_ms["encode"] - stage_ms.get("sigma_phases", 0.0)
+    enc_achieved = 512.0 * n_enc / (enc_ms * 1e-3) / 1e9
+    ta, ta_src = pmc_ta_busy(args.config)
+    line.update({
         # the dominant kernel, the training encode (k_hashgrid_fwd: 8 gathers per sample and level, 512 B per
         # ray-sample algorithmic; the longest kernel of the step from init and trained), against HBM peak; what
         # bounds it is the texture addresser, not bytes ("What bounds the forward encode")
@@ -1002,7 +1085,6 @@ def main():
                  "ms_per_launch": mlp_ms,
                  "busy": busy, "busy_source": busy_src},
         "stage_ms": stage_ms,
-        "loss": float(loss[0]),
         # the fraction of ray-samples whose dL/dsigma is exactly 0 (alpha = 1 - exp(-delta relu(sigma + n)) with
         # sigma + n <= 0, rendering_tcnn.py:252,260) over the profiled steps: they contribute exactly nothing
         "dsigma_zero_frac": zero_frac,
@@ -1014,9 +1096,7 @@ def main():
         "ert": ert,
         # the same bench on the from-init field, timed first in this run (--field trained only)
         **({"from_init": from_init} if from_init is not None else {}),
-        # the process group as torch.distributed reports it (None: a single process, no group)
-        "dist": ({"backend": dist.get_backend(), "ranks": dist.get_world_size()} if dist is not None else None),
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_rays, args.cpu_steps)
         if args.rays == "device":

@@ -48,6 +48,32 @@ def test_bench_spawns_two_gloo_ranks():
     assert line["value"] > 0 and line["loss"] == line["loss"]
 
 
+def test_plain_run_prints_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints the headline keys without the figures that take
+    steps of their own, and --dump-outputs writes the last timed step's arrays (C1: the smallest optimiser step)."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--steps", "3",
+                        "--warmup", "1", "--pretrain-windows", "1", "--dump-outputs", str(tmp_path)], env=env,
+                       capture_output=True, text=True, timeout=110, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _last_json(r.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "ray-samples/s" and line["higher_is_better"] is True and "fp16" in line["dtype"]
+    rays, samples = line["config"]["rays_per_gpu"], line["config"]["samples_per_ray"]
+    assert line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(rays * samples / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    for k in ("stage_ms", "roofline", "backward_stage", "mfma", "from_init", "cpu_baseline"):
+        assert k not in line
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"loss", "params", "occupancy_grid"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["loss"][0] == np.float32(line["loss"])
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 * 1000 * 1000
+
+
 RCCL_WORKER = r"""
 import os, sys, numpy as np, torch, torch.distributed as dist
 sys.path.insert(0, os.environ["LNR_ROOT"])

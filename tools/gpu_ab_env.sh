@@ -12,7 +12,7 @@ REP=${REP:-2}
 for rep in $(seq $REP); do
 for a in "${RUNS[@]}"; do
   for e in "${ENVS[@]}"; do
-    env $e timeout -k 10 200 python bench.py $a --no-cpu-baseline > $OUT/b.json 2> $OUT/b.err || { tail -20 $OUT/b.err; exit 1; }
+    env $e timeout -k 10 200 python bench.py $a --full --no-cpu-baseline > $OUT/b.json 2> $OUT/b.err || { tail -20 $OUT/b.err; exit 1; }
     python -c "
 import json,sys; d=json.load(open('$OUT/b.json')); s=d['stage_ms']
 print(f'[$e] [$a] {d[\"ms_per_step\"]:.4f} ms  ' + ' '.join(f'{k}={v:.4f}' for k,v in s.items()))"

@@ -13,7 +13,7 @@ libs="default $1"
 libpath() { [ "$1" = default ] && echo $R/loner_amd/_lib/libloner_amd.so || echo $R/loner_amd/_lib/variants/$1.so; }
 for rep in $(seq $REP); do
   for t in $libs; do
-    LONER_AMD_LIB=$(libpath $t) timeout -k 10 200 python bench.py $ARGS --no-cpu-baseline > $OUT/b_$t.json 2> $OUT/b_$t.err \
+    LONER_AMD_LIB=$(libpath $t) timeout -k 10 200 python bench.py $ARGS --full --no-cpu-baseline > $OUT/b_$t.json 2> $OUT/b_$t.err \
       || { tail -20 $OUT/b_$t.err; exit 1; }
     python -c "
 import json; d=json.loads(open('$OUT/b_$t.json').read().strip().splitlines()[-1]); s=d['stage_ms']

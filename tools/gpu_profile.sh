@@ -7,12 +7,12 @@ OUT=${OUT:-$R/gpurun_out}
 CFG=${1:-C2}
 cd $R
 mkdir -p $OUT
-timeout -k 10 300 python bench.py --config $CFG ${ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --config $CFG ${ARGS:-} --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/prof $OUT/pmc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- \
-  python3 $R/bench.py --config $CFG ${ARGS:-} --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err \
+  python3 $R/bench.py --config $CFG ${ARGS:-} --full --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err \
   || { tail -20 $OUT/bench_prof.err; exit 1; }
 [ "${PMC:-1}" = 1 ] || { echo profiles done; exit 0; }  # PMC=0: the bench line and the kernel trace only
 bash $R/tools/pmc_hbm.sh $CFG || exit 1

@@ -12,10 +12,10 @@ for spec in $1; do
   TAG=$CFG$(echo "$ARGS" | tr -d ' -' | sed 's/shardof/s/')
   export OUT=$R/gpurun_out/${PROF_DIR:-r3p}/$TAG ARGS
   mkdir -p $OUT
-  timeout -k 10 300 python bench.py --config $CFG $ARGS > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --config $CFG $ARGS --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
   echo "== $TAG"; cat $OUT/bench.json
   ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run \
-      --output-format csv -- python3 $R/bench.py --config $CFG $ARGS --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err ) \
+      --output-format csv -- python3 $R/bench.py --config $CFG $ARGS --full --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err ) \
     || { tail -20 $OUT/bench_prof.err; exit 1; }
   if [[ " ${PMC:-} " == *" $TAG "* ]]; then
     bash $R/tools/pmc_hbm.sh $CFG || exit 1

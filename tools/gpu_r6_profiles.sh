@@ -15,10 +15,10 @@ FC=/tmp/loner_field_$CFG.pt
 export OUT=$R/gpurun_out/$TAG/$CFG ARGS="--field-cache $FC ${EXTRA:-}"
 mkdir -p $OUT
 rm -f $FC
-timeout -k 10 400 python bench.py --config $CFG $ARGS > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --config $CFG $ARGS --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 echo "== $CFG"; python3 -c "import json; d=json.load(open('$OUT/bench.json')); print(d['ms_per_step'], d['stage_ms'])"
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run \
-    --output-format csv -- python3 $R/bench.py --config $CFG $ARGS --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err ) \
+    --output-format csv -- python3 $R/bench.py --config $CFG $ARGS --full --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err ) \
   || { tail -20 $OUT/bench_prof.err; exit 1; }
 if [ "${PMC:-0}" = 1 ]; then
   bash $R/tools/pmc_hbm.sh $CFG || exit 1

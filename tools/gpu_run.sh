@@ -38,7 +38,7 @@ for part in "$@"; do
       tail -1 $O/tests.log ;;
     bench)
       spec_args $arg
-      timeout -k 10 300 python bench.py --config $CFG $ARGS --no-cpu-baseline > $O/bench_$STAG.json 2> $O/bench_$STAG.err \
+      timeout -k 10 300 python bench.py --config $CFG $ARGS --full --no-cpu-baseline > $O/bench_$STAG.json 2> $O/bench_$STAG.err \
         || { tail -20 $O/bench_$STAG.err; exit 1; }
       python -c "
 import json; d=json.loads(open('$O/bench_$STAG.json').read().strip().splitlines()[-1]); s=d.get('stage_ms', {})
@@ -55,7 +55,7 @@ print('$STAG', round(d['ms_per_step'], 4), ' '.join(f'{k}={v:.4f}' for k, v in s
     slack)
       spec_args $arg
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d $O/trace_$STAG -o run -- python3 $R/bench.py --config $CFG $ARGS --no-cpu-baseline \
+          -d $O/trace_$STAG -o run -- python3 $R/bench.py --config $CFG $ARGS --full --no-cpu-baseline \
           > $O/trace_$STAG.json 2> $O/trace_$STAG.err ) || { tail -20 $O/trace_$STAG.err; exit 1; }
       f=$(find $O/trace_$STAG -name "*kernel_trace.csv" | head -1)
       python3 tools/join_slack.py $f | tee $O/slack_$STAG.json ;;

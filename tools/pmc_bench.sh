@@ -10,7 +10,7 @@ run() {
   D=${OUT:-$R/gpurun_out}/pmcb
   mkdir -p $D/$tag
   LONER_AMD_LIB=$LIB timeout -s KILL 120 rocprofv3 --pmc "$@" --kernel-trace --output-format csv \
-    -d $D/$tag -o run -- python3 $R/bench.py ${ARGS:-} --no-cpu-baseline --steps 10 > $D/$tag/out.txt 2>&1
+    -d $D/$tag -o run -- python3 $R/bench.py ${ARGS:-} --full --no-cpu-baseline --steps 10 > $D/$tag/out.txt 2>&1
   rc=$?
   echo "pmc $tag rc=$rc"
   [ $rc -eq 0 ] || exit $rc

@@ -13,7 +13,7 @@ run() {
   D=${OUT:-$R/gpurun_out}/pmcl2${TAG:-}
   mkdir -p $D/$tag
   timeout -s KILL 120 rocprofv3 --pmc "$@" --kernel-trace --output-format csv \
-    -d $D/$tag -o run -- python3 $R/bench.py --config $CFG ${ARGS:-} --no-cpu-baseline --steps 10 \
+    -d $D/$tag -o run -- python3 $R/bench.py --config $CFG ${ARGS:-} --full --no-cpu-baseline --steps 10 \
     > $D/$tag/out.txt 2>&1
   rc=$?
   echo "pmc $tag rc=$rc"
