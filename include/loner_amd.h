@@ -611,6 +611,34 @@ int64_t lnr_sky_rays_capacity(void);
 int lnr_sky_rays(const float* dirs, int64_t n_points, const lnr_sky_params* params, float* out, int64_t cap,
                  int32_t* count, void* stream);
 
+/* ---------------------------------------------------------------- mesh extraction (analysis/mesher.py) */
+/* The weight volume of mesher.py:139-180: every sample of weights (R,S) with weight > 0 whose ray has
+ * depth[r] < depth_max (and variance[r] < var_max when var_max > 0; variance may be NULL otherwise) and whose point
+ * o + d z (fp32) lies in [b[0], b[n - 1]] on every axis raises volume[cell] to its weight, cell = x_buck * nz +
+ * y_buck * nx * nz + z_buck (the reference's formula, kept literally: its (ny, nx, nz) layout), *_buck =
+ * torch.bucketize(point, b, right=False) = the first i with b[i] >= point.  bx[nx], by[ny], bz[nz]: DEVICE float64
+ * boundaries, non-decreasing.  volume (nx * ny * nz floats, non-negative) is ACCUMULATED with the true maximum (an
+ * integer atomic max on the weight's bits: independent of order and chunking); cells >= nx * ny * nz are dropped. */
+int lnr_volume_splat_max(const float* rays, const float* z, const float* weights, const float* depth,
+                         const float* variance, int64_t n_rays, int32_t n_samples, const double* bx, int32_t nx,
+                         const double* by, int32_t ny, const double* bz, int32_t nz, float depth_max, float var_max,
+                         float* volume, void* stream);
+/* Indexed marching cubes of volume (nx, ny, nz) fp32, C order, at `level` (a corner is inside iff value > level).
+ * Each crossed grid edge belongs to the voxel at its lower end; voxel v = (ix ny + iy) nz + iz owns up to three
+ * vertices (its edges along x, y, z, in that order) and the triangles of the cell whose lower corner it is.
+ *   _count  vert_count[v], tri_count[v] (nx ny nz int32 each)
+ *   _emit   vert_offset / tri_offset = the EXCLUSIVE scans of those counts (int64; the scan is the caller's),
+ *           n_verts / n_faces their totals: verts (n_verts, 3) = lower corner index x spacing, plus
+ *           (level - f_a) / (f_b - f_a) x spacing along the edge's axis (fp32, in this order); faces (n_faces, 3)
+ *           int32 vertex ids, in cell order then table order, wound so that normals point from inside to outside.
+ * The case table resolves a face with inside corners on one diagonal by cutting off each inside corner, from the
+ * face's own corners alone: adjacent cells agree and the mesh is closed wherever the surface avoids the border. */
+int lnr_marching_cubes_count(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level,
+                             int32_t* vert_count, int32_t* tri_count, void* stream);
+int lnr_marching_cubes_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, float sx, float sy,
+                            float sz, const int64_t* vert_offset, const int64_t* tri_offset, int64_t n_verts,
+                            int64_t n_faces, float* verts, int32_t* faces, void* stream);
+
 /* ---------------------------------------------------------------- utilities */
 /* dst[i] = lo + (hi-lo) * U(splitmix64(((uint64)seed << 32) + start + i)) */
 int lnr_fill_uniform(float* dst, int64_t n, uint32_t seed, float lo, float hi, int64_t start, void* stream);
