@@ -402,16 +402,35 @@ int lnr_field_train(const uint16_t* w, const uint32_t* enc, int64_t enc_stride, 
  * product stays >= LNR_ERT_T_MIN in list_out[0 .. *count_out) in list order (through `scratch`, at least
  * n_rays 32-bit words); the others get sigma 0 at their samples [hi, n_samples).  A ray whose product fell below
  * 1e-50 has every later
- * sample's float transmittance exactly 0 in the compositing, so its later samples' sigma and encodings cannot
- * change any output: the phases lnr_hashgrid_fwd_rays_phase -> lnr_field_sigma_phase, phase by phase (the lists
+ * sample's float transmittance 0 in the compositing, whose own double products associate differently but agree
+ * to ~1e-13 relative (the margin to float's 1.4e-45 is 1e5), so its later samples' sigma and encodings do not
+ * reach any output: the phases lnr_hashgrid_fwd_rays_phase -> lnr_field_sigma_phase, phase by phase (the lists
  * alternating between two buffers), then lnr_field_train with LNR_LP_SIGMA_READY, give the step's results without
- * evaluating them (csrc/field.hip).
+ * evaluating them.  That equivalence is empirical, not a theorem: the step is bitwise the one without termination
+ * on every field tested (tests/test_gpu_live.py), under the bound csrc/field.hip states for the later samples'
+ * alpha (factors below 1e-50 / T in the suffix sums of the samples before them).
  * lp: optional (dev_status: LNR_STATUS_SIGMA_CLIPPED for the evaluated samples; dev_step: the key). */
 int lnr_field_sigma_phase(const uint16_t* w, const uint32_t* enc, int64_t enc_stride, const float* rays,
                           const float* z, int64_t n_rays, int32_t n_samples, int32_t lo, int32_t hi, float noise_std,
                           const float* noise, uint32_t key, int64_t ray_offset, const lnr_loss_params* lp,
                           float* workspace, const uint32_t* list_in, const uint32_t* count_in, uint32_t* list_out,
                           uint32_t* count_out, double* transmittance, void* scratch, void* stream);
+/* Early ray termination, the march: what the phases lnr_hashgrid_fwd_rays_phase -> lnr_field_sigma_phase give
+ * at the bounds lo, lo + 64, ..., n_samples (lo a multiple of 64, 0 < lo < n_samples), in one launch and bitwise
+ * (tests/test_gpu_ert_march.py): for every ray of list_in[0 .. *count_in) (DEVICE: the rays alive at lo, as the
+ * phase ending at lo listed them) one workgroup encodes the ray's next 64 samples at all 16 levels into enc (the
+ * level-major array of lnr_hashgrid_fwd_rays, table = the fp16 table), evaluates their sigma into
+ * lnr_field_train's workspace, multiplies transmittance[r] by the unit's product of s = 1 - alpha + 1e-10 (the
+ * arithmetic and order of lnr_field_sigma_phase), and goes on to the next 64 while the product stays >=
+ * LNR_ERT_T_MIN; a ray that falls below gets sigma 0 at its remaining samples, whose encodings are left unwritten.
+ * The last 64 samples update nothing, as the last phase.  No list is written: transmittance[r] >= LNR_ERT_T_MIN
+ * tells which rays were still alive after sample n_samples - 64.  The sigma grid only (16 levels of 2 features).
+ * noise_std, noise, key, ray_offset, lp as lnr_field_sigma_phase. */
+int lnr_field_ert_march(const lnr_grid_desc* d, const uint16_t* table, uint32_t* enc, int64_t enc_stride,
+                        const uint16_t* w, const float* rays, const float* z, int64_t n_rays, int32_t n_samples,
+                        int32_t lo, float noise_std, const float* noise, uint32_t key, int64_t ray_offset,
+                        const lnr_loss_params* lp, float* workspace, const uint32_t* list_in,
+                        const uint32_t* count_in, double* transmittance, void* stream);
 /* Joint pose + map (optimizer.py:235-262): the per-keyframe gradient of the pose tensors [t, axis-angle] (K, 6)
  * from a step's per-sample dL/dpos01 d_pos (n_rays * n_samples, 3) (lnr_hashgrid_bwd_rays_jac) and per-ray
  * [dL/d|d|, dL/dfar] d_ray (n_rays, 2) (lnr_loss_params.dev_d_ray), for rays built as

@@ -80,6 +80,7 @@ LP_DW_OVERWRITE = 1
 LP_SIGMA_READY = 2
 LP_FORWARD_ONLY = 4
 LP_BACKWARD_ONLY = 8
+ERT_T_MIN = 1e-50  # LNR_ERT_T_MIN
 
 
 STATUS_NAN_LOSS, STATUS_INF_LOSS, STATUS_SIGMA_CLIPPED, STATUS_NONFINITE_OUTPUT = 1, 2, 4, 8
@@ -165,6 +166,9 @@ _SIGNATURES = {
                                        c_p]),
     "lnr_field_sigma_phase": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_f, c_p, c_u32,
                                              c_i64, ctypes.POINTER(LossParams), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "lnr_field_ert_march": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i32, c_i32,
+                                           c_f, c_p, c_u32, c_i64, ctypes.POINTER(LossParams), c_p, c_p, c_p, c_p,
+                                           c_p]),
     "lnr_pose_grad": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p, c_p, c_i32, c_f, c_f, c_p,
                                      c_p, c_p]),
     "lnr_pose_adam": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i64, c_f, c_f, c_f, c_f, c_p, c_p]),

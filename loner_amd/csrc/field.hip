@@ -10,6 +10,7 @@
 // Every per-sample intermediate (alpha, T, w, w_gt, dL/dw, dL/dsigma, hidden activations) lives in
 // registers/LDS; HBM sees z, the level-major encodings in, d_enc out and per-ray scalars.
 #include "common.hpp"
+#include "hashgrid.hpp"
 #include "mlp.hpp"
 
 namespace lnr {
@@ -968,6 +969,148 @@ __global__ void __launch_bounds__(kErtCompactThreads) k_ert_compact(const uint32
   if (t == 0) count_out[0] = base;
 }
 
+// Early ray termination's march (lnr_field_ert_march): the tail [lo, S) of every listed ray in one launch, in place
+// of one encode + sigma + compaction launch per 64-sample phase.  One workgroup per listed ray (a workgroup past
+// the list's end leaves at once), lane = sample of the 64-sample unit, wave w encoding levels w, w + 4, w + 8,
+// w + 12 (a mix of coherent and fine levels per wave, as the encode's level groups).  Per unit:
+//   1. every wave encodes its four levels (enc_row's corners, gathers and fmaf order: the shared helpers of
+//      hashgrid.hpp) into enc, the level-major array the backward reads, and into the unit's LDS image (4 KB);
+//   2. wave w runs the sigma MLP of tile w (samples 16 w .. 16 w + 15) on the LDS image -- the fp16 bits the stores
+//      wrote -- and leaves sigma in the workspace and in LDS;
+//   3. every wave forms the unit's product of s over its 64 lanes exactly as k_sigma_phase's wave does (per lane,
+//      then the xor butterfly, then times the carried product): the four waves compute the same bits from the same
+//      LDS values, so the stop-or-continue decision is workgroup-uniform without a further exchange, and every
+//      wave reaches every barrier;
+//   4. below t_min: sigma 0 at the ray's later samples, and the workgroup stops.
+// The two barriers per unit (after 1 and after 2) also order the reuse of the LDS image: unit k + 1's encodings are
+// written after the second barrier of unit k, which follows every read of unit k's.  The last unit updates nothing,
+// as the last phase.  No workgroup talks to another.  Bitwise the phased sequence at 64-sample bounds
+// (tests/test_gpu_ert_march.py).
+struct MarchLevels {
+  LevelParams lv[kSigmaLevels];
+};
+constexpr int kMarchPitch = 68;  // words per level of the LDS image: lanes 16 g + c of the MLP read hit 32 banks
+#ifndef LNR_MARCH_WAVES
+#define LNR_MARCH_WAVES 8  // waves per SIMD asked of the march (64 VGPRs, no scratch).  Measured at C2, march from
+                           // sample 256 (0.48 M ray-samples): 162 us so; 161 us with two levels' gathers in flight per
+                           // wave at 6 waves (80 VGPRs) and with four at 5 waves (96): neither latency nor occupancy
+                           // bounds it, the 16-level gather working set does
+#endif
+// The forward's sigma weights kept in LDS ([operand][64 lanes] of 16 B, as SigmaWeightsLds; 6 KB per workgroup):
+// layer 0's four A operands and the output layer's two, read where used instead of held in 24 registers (with
+// them in registers the kernel takes 96 VGPRs, 5 waves per SIMD; from LDS 64 and 8, no scratch either way).
+struct MarchWeightsLds {
+  const half8_t* p;
+  __device__ __forceinline__ half8_t A0(int t) const { return p[t * 64 + (threadIdx.x & 63)]; }
+  __device__ __forceinline__ float w1(int k) const { return (float)p[(4 + (k >> 3)) * 64 + (threadIdx.x & 63)][k & 7]; }
+  __device__ __forceinline__ void stage(half8_t* lds, const SigmaWeights& sw) {
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x < 64) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) lds[t * 64 + lane] = sw.a0[t];
+      lds[4 * 64 + lane] = sw.w1h[0];
+      lds[5 * 64 + lane] = sw.w1h[1];
+    }
+    p = lds;
+  }
+};
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MARCH_WAVES)))
+k_ert_march(FieldArgs a, MarchLevels ml, const uint32_t* __restrict__ table, uint32_t* __restrict__ enc,
+            const uint32_t* __restrict__ list, const uint32_t* __restrict__ count, int32_t lo,
+            double* __restrict__ trans, double t_min) {
+  if (blockIdx.x >= count[0]) return;  // (block-uniform) past the listed rays
+  __shared__ uint32_t encb[kSigmaLevels * kMarchPitch];
+  __shared__ float sigb[kSigmaFwdUnit];
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int S = a.S;
+  const int64_t r = (int64_t)list[blockIdx.x];
+  const float* ry = a.rays + 13 * r;
+  const PosFromRays pos{a.rays, a.z, S};
+  const PosFromRays::Raw ray{ry[0], ry[1], ry[2], ry[3], ry[4], ry[5], 0.f};
+  const float dnorm = sqrtf(ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz);
+  const float* zr = a.z + r * S;
+  const uint32_t gr = (uint32_t)(a.ray_offset + r);
+  __shared__ half8_t wlds[6 * 64];
+  MarchWeightsLds sw;
+  {
+    SigmaWeights sr;
+    load_sigma_weights(a.w, sr);
+    sw.stage(wlds, sr);  // (published by the first unit's barrier, before the first MLP)
+  }
+  double t = trans[r];
+  bool clipped = false;
+  for (int u0 = lo; u0 < S; u0 += kSigmaFwdUnit) {
+    const int i = u0 + lane;
+    const int64_t n = r * S + i;
+    const float zi = zr[i];
+    PosFromRays::Raw q = ray;
+    q.t = zi;
+    float x, y, z;
+    pos.eval(q, x, y, z);
+    for (int k = 0; k < kSigmaLevels / NW; ++k) {
+      const int l = wid + NW * k;
+      const LevelParams& lv = ml.lv[l];
+      uint32_t word;
+      if (lv.fine) {  // wave-uniform
+        FineCell fc;
+        uint32_t v[8];
+        fine_cell(lv, x, y, z, fc);
+        fine_gather_paired(table + lv.offset, fc, true, v);
+        word = enc_blend_fine(fc, v);
+      } else {
+        Corners cn;
+        uint32_t v[8];
+        level_corners(lv, x, y, z, cn);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = table[cn.idx[j]];
+        word = enc_blend(cn, v);
+      }
+      store_enc(enc + (int64_t)l * a.enc_stride + n, word);
+      encb[l * kMarchPitch + lane] = word;
+    }
+    lds_barrier();
+    half8_t b;  // load_enc_operand's layout for sample 16 wid + c, from the LDS image
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t v = encb[(4 * g + j) * kMarchPitch + 16 * wid + c];
+      b[2 * j + 0] = __builtin_bit_cast(_Float16, (uint16_t)(v & 0xFFFFu));
+      b[2 * j + 1] = __builtin_bit_cast(_Float16, (uint16_t)(v >> 16));
+    }
+    SigmaHidden h;
+    const float sgm = sigma_tile_fwd(sw, b, h);
+    const float sg16 = sigma_to_f16(sgm);
+    if (g == 0) {
+      a.d_sigma[r * S + u0 + 16 * wid + c] = sg16;
+      sigb[16 * wid + c] = sg16;
+    }
+    clipped |= !isfinite(round_f16(sgm));
+    if (u0 + kSigmaFwdUnit >= S) break;  // the last unit: nothing left to decide
+    lds_barrier();
+    {  // k_sigma_phase's transmittance update of a 64-sample phase, in every wave
+      const float mine = sigb[lane];
+      const float dl = (i + 1 < S) ? (zr[i + 1] - zi) : 1e10f;
+      const float delta = dl * dnorm;
+      float nz = 0.f;
+      if (a.noise) nz = a.noise[n] * a.noise_std;
+      else if (a.noise_std > 0.f) nz = rand_normal(step_key_of(a), kStreamNoise, gr, (uint32_t)i) * a.noise_std;
+      const float sr = fmaxf(mine + nz, 0.f);
+      const float alpha = 1.0f - expf(-(delta * sr));
+      double P = 1.0;
+      P *= (double)((1.0f - alpha) + 1e-10f);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) P *= __shfl_xor(P, o, 64);
+      t = t * P;
+    }
+    if (threadIdx.x == 0) trans[r] = t;
+    if (!(t >= t_min)) {  // (workgroup-uniform) terminated here: sigma 0 for the samples the march leaves out
+      for (int j = u0 + kSigmaFwdUnit + (int)threadIdx.x; j < S; j += NT) a.d_sigma[r * S + j] = 0.f;
+      break;
+    }
+  }
+  if (a.lp.dev_status && __any(clipped) && lane == 0) atomicOr(a.lp.dev_status, LNR_STATUS_SIGMA_CLIPPED);
+}
+
 // Phase 1b, one wave per ray: compositing -> loss -> compositing backward on the sigma of phase 1a,
 // dL/dsigma written over it (a.d_sigma, (R, S) fp32).
 template <int C>
@@ -1749,6 +1892,37 @@ extern "C" int lnr_field_sigma_phase(const uint16_t* w, const uint32_t* enc, int
   if (hi < n_samples)
     hipLaunchKernelGGL(k_ert_compact, dim3(1), dim3(kErtCompactThreads), 0, st, keep, cin, n_rays, list_out, count_out);
   LNR_RETURN_LAUNCH("lnr_field_sigma_phase");
+}
+
+extern "C" int lnr_field_ert_march(const lnr_grid_desc* d, const uint16_t* table, uint32_t* enc, int64_t enc_stride,
+                                   const uint16_t* w, const float* rays, const float* z, int64_t n_rays,
+                                   int32_t n_samples, int32_t lo, float noise_std, const float* noise, uint32_t key,
+                                   int64_t ray_offset, const lnr_loss_params* lp, float* workspace,
+                                   const uint32_t* list_in, const uint32_t* count_in, double* transmittance,
+                                   void* stream) {
+  if (int e = check_rays(rays, z, n_rays, n_samples, "lnr_field_ert_march")) return e;
+  LNR_REQUIRE(d != nullptr && d->n_levels == (uint32_t)kSigmaLevels && d->n_features == 2,
+              "lnr_field_ert_march: the sigma grid has %d levels of 2 features", kSigmaLevels);
+  LNR_REQUIRE(n_samples % 64 == 0 && lo > 0 && lo < n_samples && lo % 64 == 0,
+              "lnr_field_ert_march: the march from %d of %d samples must start and end on whole 64-sample waves", lo,
+              n_samples);
+  LNR_REQUIRE(enc_stride >= n_rays * (int64_t)n_samples && enc_stride < (int64_t(1) << 26),
+              "lnr_field_ert_march: bad enc_stride");
+  LNR_REQUIRE(n_rays < (int64_t(1) << 31), "lnr_field_ert_march: too many rays");
+  if (n_rays == 0) return LNR_OK;
+  LNR_REQUIRE(table && enc && w && workspace && list_in && count_in && transmittance,
+              "lnr_field_ert_march: null pointer");
+  FieldArgs a{};
+  a.w = w; a.enc = enc; a.enc_stride = enc_stride; a.rays = rays; a.z = z; a.n_rays = n_rays; a.S = n_samples;
+  a.noise_std = noise_std; a.noise = noise; a.key = key; a.ray_offset = ray_offset;
+  if (lp) a.lp = *lp;
+  a.d_sigma = workspace + lnr_dw_workspace_words(n_rays);
+  const GridArgs ga = make_args(d, n_samples);
+  MarchLevels ml;
+  for (int l = 0; l < kSigmaLevels; ++l) ml.lv[l] = ga.lv[l];
+  hipLaunchKernelGGL(k_ert_march, dim3((unsigned)n_rays), dim3(NT), 0, as_stream(stream), a, ml,
+                     reinterpret_cast<const uint32_t*>(table), enc, list_in, count_in, lo, transmittance, kErtTMin);
+  LNR_RETURN_LAUNCH("lnr_field_ert_march");
 }
 
 extern "C" int lnr_field_render(const uint16_t* w, const uint32_t* enc, int64_t enc_stride, const float* rays,

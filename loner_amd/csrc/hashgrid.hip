@@ -17,11 +17,6 @@
 
 namespace lnr {
 
-// The encoding is written once, as whole lines, and read by the field kernels after this launch: a
-// nontemporal store keeps it out of the way of the table slices in L2 (step -0.01 ms at C2; plain stores
-// re-measured in round 5 within the noise)
-__device__ __forceinline__ void store_enc(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, p); }
-
 // The 8 corners of a fine (hashed, power-of-two) level: the x-pairs e, e ^ d of the four y/z edges.
 // What bounds this gather is the texture addresser: TA busy 0.78 of the launch at C2 with the level-grouped
 // encode (profiles/r04_l2req_C2.txt; 0.85 before the grouping, profiles/r03_l2req_C2.txt), about 40 TA cycles
@@ -34,46 +29,6 @@ __device__ __forceinline__ void fine_gather(const uint32_t* __restrict__ tl, con
   for (int j = 0; j < 4; ++j) {
     v[2 * j] = tl[c.e[j]];
     v[2 * j + 1] = tl[c.e[j] ^ c.d];
-  }
-}
-
-// The same 8 corners with lanes paired (2m, 2m + 1): in one instruction both lanes of a pair read
-// the two x-corners of one sample's edge (the even lane corner e, the odd lane e ^ d), so the pair
-// shares a cache line (94 % of the x-pairs do) and a wave-wide gather touches 32 lines instead of 64.
-// Slot 0 of each edge serves the even lane's sample, slot 1 the odd lane's; one DPP swap per edge
-// hands each lane the corner its partner read for it.  C2 encode 0.721 -> 0.691 ms: the texture
-// addresser does not charge purely by lines.  Every lane of the wave must take
-// part (the swaps): the loads, not the lanes, are predicated on ``use``, and a dead lane still gathers
-// for a live partner, which is why the live-masked eval launch keeps fine_gather.  Same entries in the
-// same corner order: the encoding is bit-identical to fine_gather's.
-#ifndef LNR_ENC_PAIRED
-#define LNR_ENC_PAIRED true  // the training / plain eval encode's fine gathers lane-paired (C2: 0.721 -> 0.691 ms)
-#endif
-__device__ __forceinline__ uint32_t dpp_pair_swap(uint32_t v) {  // quad_perm [1, 0, 3, 2]
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
-}
-__device__ __forceinline__ void fine_gather_paired(const uint32_t* __restrict__ tl, const FineCell& c, bool use,
-                                                   uint32_t (&v)[8]) {
-  const bool odd = (threadIdx.x & 1) != 0;
-  const uint32_t pd = dpp_pair_swap(c.d);
-  const bool puse = dpp_pair_swap(use ? 1u : 0u) != 0u;
-  const uint32_t d_even = odd ? pd : c.d, d_odd = odd ? c.d : pd;
-  const bool use_even = odd ? puse : use, use_odd = odd ? use : puse;
-  uint32_t s0[4], s1[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t pe = dpp_pair_swap(c.e[j]);
-    const uint32_t e_even = odd ? pe : c.e[j], e_odd = odd ? c.e[j] : pe;
-    const uint32_t a0 = odd ? (e_even ^ d_even) : e_even;  // slot 0: the even lane's sample
-    const uint32_t a1 = odd ? (e_odd ^ d_odd) : e_odd;     // slot 1: the odd lane's sample
-    s0[j] = use_even ? tl[a0] : 0u;
-    s1[j] = use_odd ? tl[a1] : 0u;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t r = dpp_pair_swap(odd ? s0[j] : s1[j]);  // what the partner read for this lane
-    v[2 * j] = odd ? r : s0[j];
-    v[2 * j + 1] = odd ? s1[j] : r;
   }
 }
 

@@ -190,6 +190,16 @@ AR_CUT_TWO_GROUPS = 8
 # ray-sample ERT_SAMPLE_NS, phased or not; going phased ERT_FIXED_US; every phase after the first ERT_PHASE_US (its
 # encode, sigma and list launches, latency-bound when few rays are left)
 ERT_SAMPLE_NS, ERT_FIXED_US, ERT_PHASE_US = 0.150, 5.0, 28.0
+# The march (lnr_field_ert_march): a plan's trailing run of two or more 64-sample phases runs as one launch, a
+# workgroup per ray still alive marching 64 samples at a time.  Its cost: ERT_MARCH_FIXED_US for the launch plus
+# ERT_MARCH_SAMPLE_NS per ray-sample marched, each unit over the rays alive at its start; fitted to the traced C2
+# marches from samples 256 (0.48 M ray-samples, 161 us) and 192 (0.89 M, 274 us).  At
+# nearly twice the phases' rate per sample (all 16 levels' gathers share an XCD's L2) a march pays for a short
+# tail only: on the trained C2 field the planner takes [0, 320, 384, 448, 512], and the bench step went from
+# 0.913 to 0.892 ms (medians of four interleaved runs each, every run faster).  LONER_ERT_MARCH=0 turns it off: a
+# trailing run of 64-sample phases then goes phase by phase, and ert_plan proposes no march plan.
+ERT_MARCH_SAMPLE_NS, ERT_MARCH_FIXED_US = 0.278, 27.0
+ERT_MARCH = os.environ.get("LONER_ERT_MARCH", "1") != "0"
 TERM_HIST_SLOTS = 256  # LNR_TERM_HIST_SLOTS
 ERT_MAX_CUTS = 4
 ERT_MARGIN = 0.02  # eager steps: a plan replaces the current one only when modelled this much faster (of the full
@@ -208,37 +218,59 @@ def ert_alive(hist, S):
     return tail / tot
 
 
-def ert_cost_us(bounds, alive, S, n_samples):
+def ert_march_start(bounds):
+    """The index i >= 1 into ``bounds`` ([0, c1, .., S] or None) at which the plan's trailing run of 64-sample
+    phases starts, when that run has two or more phases (the march takes bounds[i:]; the first phase, every ray,
+    stays on the dense encode), or None."""
+    if bounds is None:
+        return None
+    i = len(bounds) - 1
+    while i > 1 and bounds[i] - bounds[i - 1] == 64:
+        i -= 1
+    return i if len(bounds) - 1 - i >= 2 else None
+
+
+def ert_cost_us(bounds, alive, S, n_samples, march=None):
     """Modelled encode + sigma time of one step (n_samples ray-samples) with the phases ``bounds``
-    ([0, c1, .., S]) or, for None, without early ray termination."""
+    ([0, c1, .., S]) or, for None, without early ray termination.  ``march`` (default: ERT_MARCH): a trailing run
+    of 64-sample phases (ert_march_start) is priced as the one march launch that executes it."""
     full = ERT_SAMPLE_NS * 1e-3 * n_samples
     if bounds is None:
         return full
-    t = ERT_FIXED_US + ERT_PHASE_US * (len(bounds) - 2)
-    for lo, hi in zip(bounds[:-1], bounds[1:]):
+    i0 = ert_march_start(bounds) if (ERT_MARCH if march is None else march) else None
+    n_ph = len(bounds) - 1 if i0 is None else i0  # the phases run as launches of their own
+    t = ERT_FIXED_US + ERT_PHASE_US * (n_ph - 1)
+    for lo, hi in zip(bounds[:n_ph], bounds[1:n_ph + 1]):
         t += full * float(alive[lo // 64]) * (hi - lo) / S
+    if i0 is not None:
+        t += ERT_MARCH_FIXED_US
+        for lo in bounds[i0:-1]:
+            t += ERT_MARCH_SAMPLE_NS * 1e-3 * n_samples * float(alive[lo // 64]) * 64 / S
     return t
 
 
-def ert_plan(hist, S, n_samples, current=None, max_cuts=ERT_MAX_CUTS, margin=ERT_MARGIN):
+def ert_plan(hist, S, n_samples, current=None, max_cuts=ERT_MAX_CUTS, margin=ERT_MARGIN, march=None):
     """The early-ray-termination phases for the coming steps from the last steps' termination histogram: the
-    cheapest under ert_cost_us among no termination and every set of at most ``max_cuts`` cuts at multiples of
-    64 samples, kept only if it beats ``current`` (the plan in use: bounds or None) by ``margin`` of the full
-    encode (so the graphs, captured per plan, are not re-captured for noise).  Returns bounds or None."""
+    cheapest under ert_cost_us among no termination, every set of at most ``max_cuts`` cuts at multiples of
+    64 samples and (``march``, default ERT_MARCH) every march plan [0, c1, c1 + 64, .., S], kept only if it beats
+    ``current`` (the plan in use: bounds or None) by ``margin`` of the full encode (so the graphs, captured per
+    plan, are not re-captured for noise).  Returns bounds or None."""
     import itertools
     if S % 64 or S < 128:
         return None
+    march = ERT_MARCH if march is None else march
     alive = ert_alive(hist, S)
-    full = ert_cost_us(None, alive, S, n_samples)
+    full = ert_cost_us(None, alive, S, n_samples, march)
     pos = list(range(64, S, 64))
     best, best_t = None, full
-    for k in range(1, min(max_cuts, len(pos)) + 1):
-        for cuts in itertools.combinations(pos, k):
-            b = [0, *cuts, S]
-            t = ert_cost_us(b, alive, S, n_samples)
-            if t < best_t:
-                best, best_t = b, t
-    cur_t = ert_cost_us(current, alive, S, n_samples)
+    cands = [[0, *cuts, S] for k in range(1, min(max_cuts, len(pos)) + 1) for cuts in itertools.combinations(pos, k)]
+    if march:
+        cands += [[0, *range(c1, S + 1, 64)] for c1 in pos[:-1]]
+    for b in cands:
+        t = ert_cost_us(b, alive, S, n_samples, march)
+        if t < best_t:
+            best, best_t = b, t
+    cur_t = ert_cost_us(current, alive, S, n_samples, march)
     return best if best_t < cur_t - margin * full else current
 
 
@@ -428,14 +460,18 @@ class StepEngine:
         # compositing, so its weight is 0 and neither its sigma nor its encoding can change any output
         # (csrc/field.hip, LNR_ERT_T_MIN; 45 % of a trained C2 batch lies behind T = 0, tools/dead_bound.py).  The
         # forward then runs in phases of samples per ray (ert_bounds): each phase encodes and evaluates the rays still
-        # alive and updates their transmittance, and a ray below 1e-50 skips the later phases.  Bitwise the step
-        # without it (tests/test_gpu_live.py).  LONER_ERT: auto (default): the compositing counts where every ray
-        # terminates (term_hist, lnr_loss_params.dev_term_hist), read back like the live backward's probe (no host
-        # sync), and ert_plan picks the phases, or none, from the last steps' counts under a fitted cost model
+        # alive and updates their transmittance, and a ray below 1e-50 skips the later phases.  Empirically bitwise
+        # the step without it (tests/test_gpu_live.py; not a theorem: the compositing's double products associate
+        # differently, csrc/field.hip gives the bound that keeps the skipped samples out of every float result).
+        # With ert_march (on unless LONER_ERT_MARCH=0, see ERT_MARCH) a plan's trailing run of 64-sample phases runs
+        # as one launch, the march (lnr_field_ert_march), bitwise the phases.
+        # LONER_ERT: auto (default): the compositing counts where every ray terminates (term_hist,
+        # lnr_loss_params.dev_term_hist), read back like the live backward's probe (no host sync), and ert_plan picks the phases, or none, from the last steps' counts under a fitted cost model
         # (on the trained C2 field three cuts, on C4's forest, where few rays terminate,
         # none); 1: always, at the fixed cuts LONER_ERT_CUTS (fractions of n_samples, default 0.5,0.625,0.75); 0: never.
         self.ert = {"0": False, "1": True}.get(os.environ.get("LONER_ERT", "auto"), "auto")
         self.ert_cuts = [float(v) for v in os.environ.get("LONER_ERT_CUTS", "0.5,0.625,0.75").split(",") if v.strip()]
+        self.ert_march = ERT_MARCH
         # the phases' device state: the lists of rays still alive (two buffers, alternating), their counts, the
         # transmittance products and a scratch word per ray
         self.ert_lists = torch.zeros(2, max(n_rays, 1), dtype=torch.int32, device=dev)
@@ -444,6 +480,7 @@ class StepEngine:
         self.ert_keep = torch.zeros(max(n_rays, 1), dtype=torch.int32, device=dev)
         self._ert_est = None  # auto: the plan's alive shares after each 64-sample boundary (the encode's grid hints)
         self._ert_last = None  # the phases of the last step (tests, tools)
+        self._ert_marched = None  # where the last step's march started (an index into its phases), or None
         self._ert_plan = None  # auto: the phases in use, [0, c1, .., S], or None
         self._ert_next = None  # auto: (plan, alive shares) waiting for the next window (graph replay)
         nb = self.S // 64 + 1
@@ -495,15 +532,19 @@ class StepEngine:
 
     def ert_alive_last(self):
         """The share of the last step's rays still alive after its last cut (early ray termination), or 1.0
-        without phases (a host sync: tests and tools)."""
+        without phases (a host sync: tests and tools).  A marched plan writes no lists: the share is counted from
+        the transmittance products the march left, the rays with T >= LNR_ERT_T_MIN after the last cut -- the
+        same rays the last list would hold."""
         b = self._ert_last
         if b is None or len(b) < 3:
             return 1.0
+        if self._ert_marched is not None:
+            return int((self.ert_T[:self._r_last] >= L.ERT_T_MIN).sum().item()) / max(self._r_last, 1)
         return int(self.ert_counts[(len(b) - 3) % 2].item()) / max(self._r_last, 1)
 
     def _ert_key(self):
         b = self.ert_bounds()
-        return None if b is None else tuple(b)
+        return None if b is None else (tuple(b), bool(self.ert_march))
 
     def ert_probe(self):
         """LONER_ERT=auto: re-plan the phases from the termination counts the steps since the last probe added to
@@ -523,7 +564,7 @@ class StepEngine:
                 # (no margin for those: the cheapest plan of the latest counts)
                 defer = self._ert_est is not None and self._graph_window is not None
                 plan = ert_plan(d, self.S, self._r_last * self.S, self._ert_plan,
-                                margin=0.0 if defer else ERT_MARGIN)
+                                margin=0.0 if defer else ERT_MARGIN, march=self.ert_march)
                 if plan != self._ert_plan or self._ert_est is None:
                     # the alive shares behind the encode's grid hints: refreshed with the plan only (the graphs,
                     # captured per plan, hold the hints of their capture)
@@ -696,11 +737,17 @@ class StepEngine:
         fwd_hist = self.count_in_forward and not self._live
         ert = self.ert_bounds()
         self._ert_last = ert
+        i0 = ert_march_start(ert) if self.ert_march else None
+        self._ert_marched = i0
         if ert is not None:
             # early ray termination (see __init__): phase by phase, the encode and sigma of the rays still alive
-            # (the list phase q - 1 left; every ray in phase 0; a ray that terminates gets sigma 0 at its later samples)
+            # (the list phase q - 1 left; every ray in phase 0; a ray that terminates gets sigma 0 at its later samples);
+            # then the march over the plan's trailing 64-sample phases, from the list the last phase before it left
+            # (a profiled march step keeps every launch inside the "encode" pair: bench.py scales the
+            # "sigma_phase" pairs by the plan's phases, which the march does not launch)
             lp.flags |= L.LP_SIGMA_READY
-            for q in range(len(ert) - 1):
+            mp = prof if i0 is None else None
+            for q in range(len(ert) - 1 if i0 is None else i0):
                 lo, hi = ert[q], ert[q + 1]
                 hist = q == 0 and fwd_hist
                 lin = None if q == 0 else self.ert_lists[(q - 1) % 2]
@@ -710,11 +757,16 @@ class StepEngine:
                 L.call("lnr_hashgrid_fwd_rays_phase", L.ctypes.byref(st.desc), rays, self.z, R, S, st.table_f16,
                        self.enc, N, self.bwd_ws if hist else None, self.bwd_ws_bytes if hist else 0, lin, cin,
                        expect, lo, hi, s)
-                m(prof, "sigma_phase")
+                m(mp, "sigma_phase")
                 L.call("lnr_field_sigma_phase", st.mlp_f16, self.enc, N, rays, self.z, R, S, lo, hi,
                        cfg.raw_noise_std, noise, key, self.ray_offset, L.ctypes.byref(lp), self.ws, lin, cin,
                        self.ert_lists[q % 2], self.ert_counts[q % 2:q % 2 + 1], self.ert_T, self.ert_keep, s)
-                m(prof, "sigma_phase")
+                m(mp, "sigma_phase")
+            if i0 is not None:
+                q = i0 - 1
+                L.call("lnr_field_ert_march", L.ctypes.byref(st.desc), st.table_f16, self.enc, N, st.mlp_f16, rays,
+                       self.z, R, S, ert[i0], cfg.raw_noise_std, noise, key, self.ray_offset, L.ctypes.byref(lp),
+                       self.ws, self.ert_lists[q % 2], self.ert_counts[q % 2:q % 2 + 1], self.ert_T, s)
         elif fwd_hist:
             L.call("lnr_hashgrid_fwd_rays", L.ctypes.byref(st.desc), rays, self.z, R, S, st.table_f16, self.enc, N,
                    self.bwd_ws, self.bwd_ws_bytes, s)
