@@ -658,6 +658,46 @@ int lnr_marching_cubes_emit(const float* volume, int32_t nx, int32_t ny, int32_t
                             float sz, const int64_t* vert_offset, const int64_t* tri_offset, int64_t n_verts,
                             int64_t n_faces, float* verts, int32_t* faces, void* stream);
 
+/* ---------------------------------------------------------------- frame-to-frame tracking (src/tracking/tracker.py) */
+/* Normals of a cloud, Open3D's estimate_normals() with KDTreeSearchParamKNN(k): for each point of pts (n, 3) its exact k
+ * nearest neighbours in the same cloud (itself included), ordered by (squared fp32 distance, index); the covariance
+ * about their mean and the unit eigenvector of its smallest eigenvalue in fp64, turned towards the origin
+ * (normal . point <= 0); (0, 0, 1) when the covariance is all zero.  3 <= k <= 64, k <= n <= 2^18; the work is O(n^2). */
+int lnr_cloud_normals(const float* pts, int64_t n, int32_t k, float* normals, void* stream);
+
+/* Point-to-plane ICP (Open3D's registration_icp with TransformationEstimationPointToPlane) as a schedule of kernels
+ * around a device-resident state.  T (row-major 4x4) maps source points into the target's frame. */
+#define LNR_ICP_MAX_POINTS (1 << 24)
+typedef struct lnr_icp_state {
+  double T[16];
+  double fitness;     /* kept pairs / n_src of the last evaluation */
+  double rmse;        /* sqrt(sum d^2 / kept pairs) of the last evaluation, 0 without pairs */
+  double sum_d2;
+  double sums[27];    /* the last evaluation's J^T J (upper triangle, row-major, 21) and J^T r (6) */
+  int64_t n_corr;
+  int32_t iterations; /* updates applied in this stage */
+  int32_t converged;
+} lnr_icp_state;
+int64_t lnr_icp_workspace_bytes(int64_t n_src);  /* 0 for an n_src outside [1, LNR_ICP_MAX_POINTS] */
+/* state <- {T0 (16 HOST doubles, copied before the call returns), everything else 0}. */
+int lnr_icp_init(lnr_icp_state* state, const double* T0, void* stream);
+/* One stage from the state's T: max_iterations + 1 rounds of two kernels, all enqueued by this call.
+ *   correspond  p = T s in fp64; the nearest target point q of p rounded to fp32, by (squared fp32 distance, index);
+ *               the pair is kept iff d^2 < threshold^2 (fp32).  Kept pairs add J^T J, J^T r (J = [p x n, n],
+ *               r = (p - q) . n, n = q's normal; fp64), 1 to the count and |p - q|^2 to sum d^2, as one row of
+ *               partial sums per block in the workspace.  corr_idx (n_src int32, -1 = none) and corr_d2 (n_src fp32,
+ *               0 = none) are written when not NULL.
+ *   update      the rows added in a fixed order; fitness and rmse; from the second round on, converged iff
+ *               |fitness - previous| < rel_fitness and |rmse - previous| < rel_rmse; otherwise, while fewer than
+ *               max_iterations updates were applied, T <- M(x) T with J^T J x = -J^T r (6x6 Cholesky, fp64) and
+ *               M = Rz(x2) Ry(x1) Rx(x0) | x3..5.  Fewer than 6 pairs or a failed solve leave T as it is.
+ * Rounds after convergence do nothing.  The first round clears `converged` and `iterations` and keeps T, so stages
+ * chain without a host decision; the results repeat bit for bit.  workspace: lnr_icp_workspace_bytes(n_src) bytes,
+ * 8-byte aligned. */
+int lnr_icp_stage(const float* src, int64_t n_src, const float* tgt, const float* tgt_normals, int64_t n_tgt,
+                  float threshold, int32_t max_iterations, double rel_fitness, double rel_rmse, lnr_icp_state* state,
+                  void* workspace, int64_t ws_bytes, int32_t* corr_idx, float* corr_d2, void* stream);
+
 /* ---------------------------------------------------------------- utilities */
 /* dst[i] = lo + (hi-lo) * U(splitmix64(((uint64)seed << 32) + start + i)) */
 int lnr_fill_uniform(float* dst, int64_t n, uint32_t seed, float lo, float hi, int64_t start, void* stream);

@@ -121,6 +121,13 @@ class SkyParams(ctypes.Structure):
     _fields_ = [("rot", ctypes.c_float * 9), ("top_rows", ctypes.c_int32), ("horizon_deg", ctypes.c_float)]
 
 
+class IcpState(ctypes.Structure):
+    """``lnr_icp_state``: the device-resident state of the ICP schedule."""
+    _fields_ = [("T", ctypes.c_double * 16), ("fitness", ctypes.c_double), ("rmse", ctypes.c_double),
+                ("sum_d2", ctypes.c_double), ("sums", ctypes.c_double * 27), ("n_corr", ctypes.c_int64),
+                ("iterations", ctypes.c_int32), ("converged", ctypes.c_int32)]
+
+
 _SIGNATURES = {
     "lnr_version": (ctypes.c_int, []),
     "lnr_last_error": (ctypes.c_char_p, []),
@@ -213,6 +220,11 @@ _SIGNATURES = {
     "lnr_marching_cubes_count": (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_f, c_p, c_p, c_p]),
     "lnr_marching_cubes_emit": (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f, c_p, c_p, c_i64, c_i64,
                                                c_p, c_p, c_p]),
+    "lnr_cloud_normals": (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_p]),
+    "lnr_icp_workspace_bytes": (c_i64, [c_i64]),
+    "lnr_icp_init": (ctypes.c_int, [c_p, ctypes.POINTER(c_d), c_p]),
+    "lnr_icp_stage": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_f, c_i32, c_d, c_d, c_p, c_p, c_i64, c_p, c_p,
+                                     c_p]),
     "lnr_fill_uniform": (ctypes.c_int, [c_p, c_i64, c_u32, c_f, c_f, c_i64, c_p]),
     "lnr_f32_to_f16": (ctypes.c_int, [c_p, c_p, c_i64, c_p]),
 }

@@ -137,7 +137,8 @@ class Optimizer:
         window's rays; the opaque count and the gradients are summed with ``allreduce(t,
         async_op=...)`` (e.g. ``torch.distributed.all_reduce``), so every rank holds the same map.
         ``fixed_poses``: run joint pose + map iteration configs as map-only ones with the poses held
-        fixed (otherwise they raise NotImplementedError; see the module docstring)."""
+        fixed, with a warning (otherwise they optimise the poses on the fused step, ``loner_amd.pose``; see
+        the module docstring)."""
         if world_cube is None:
             raise ValueError("Optimizer needs the world cube")
         self._settings = settings

@@ -1,0 +1,131 @@
+"""Track synthetic scans along a small-motion trajectory with loner_amd.tracking.Tracker (GPU box) and report, per
+frame, the translation and rotation error against the generating poses, the final drift, HIP-event times of the
+normals kernel and of the two-stage ICP schedule, and beside them the wall time and the poses of the numpy / scipy
+restatement (normals_reference, icp_schedule_reference) on the same clouds.
+
+    python tools/track_demo.py [--kind quad] [--scans 8] [--points 5000] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def step_pose(i):
+    """The i-th step of the trajectory: about 0.4 m forward with 2 deg of yaw and 0.5 deg of pitch, varied a little
+    from step to step."""
+    y, p = np.deg2rad(2.0 + 0.3 * np.sin(i)), np.deg2rad(0.5 * np.cos(0.7 * i))
+    Rz = np.array([[np.cos(y), -np.sin(y), 0], [np.sin(y), np.cos(y), 0], [0, 0, 1]])
+    Ry = np.array([[np.cos(p), 0, np.sin(p)], [0, 1, 0], [-np.sin(p), 0, np.cos(p)]])
+    T = np.eye(4)
+    T[:3, :3] = Rz @ Ry
+    T[:3, 3] = (0.4 + 0.05 * np.cos(i), 0.04 * np.sin(1.3 * i), 0.02)
+    return T
+
+
+def pose_error(T, ref):
+    d = np.linalg.inv(ref) @ T
+    ang = np.degrees(np.arccos(np.clip((np.trace(d[:3, :3]) - 1) / 2, -1, 1)))
+    return float(np.linalg.norm(d[:3, 3])), float(ang)
+
+
+def event_ms(fn, reps=5):
+    """Median HIP-event time of fn() over reps runs after one warm-up."""
+    fn()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return float(np.median(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", default="quad", choices=("quad", "canteen"))
+    ap.add_argument("--scans", type=int, default=8)
+    ap.add_argument("--points", type=int, default=5000)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    from loner_amd import synthetic as syn
+    from loner_amd import tracking as TR
+    dev = torch.device("cuda", 0)
+    poses = [syn.keyframe_poses(args.kind, 1, None)[0]]
+    for i in range(args.scans - 1):
+        poses.append(poses[-1] @ step_pose(i))
+    win = syn.make_window(args.kind, args.scans, seed=3, poses=poses)
+    settings = TR.TrackerSettings(target_uniform_point_count=args.points)
+    tracker = TR.Tracker(settings, dev)
+    solver = TR.IcpSolver(dev)
+    frames, ref_pose, prev, prev_dev = [], np.eye(4), None, None
+    for i, w in enumerate(win):
+        truth = np.linalg.inv(poses[0]) @ poses[i]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = tracker.track(dict(directions=w["directions"], distances=w["distances"]))
+        torch.cuda.synchronize()
+        wall_gpu = time.perf_counter() - t0
+        # the same cloud through the float64 restatement
+        pts = TR.frame_point_cloud(w["directions"], w["distances"], target_points=args.points)
+        t0 = time.perf_counter()
+        nrm = TR.normals_reference(pts.numpy(), settings.knn)
+        t_nrm = time.perf_counter() - t0
+        t_icp, ref_it = 0.0, []
+        if prev is not None:
+            t0 = time.perf_counter()
+            T, res = TR.icp_schedule_reference(pts.numpy(), prev[0], prev[1], settings.schedule)
+            t_icp = time.perf_counter() - t0
+            ref_pose = ref_pose @ T
+            ref_it = [r["iterations"] for r in res]
+        # the kernels alone, event-timed
+        pd = pts.to(dev)
+        nd = torch.empty_like(pd)
+        ms_nrm = event_ms(lambda: TR.cloud_normals(pd, settings.knn, nd))
+        ms_icp = 0.0
+        if prev_dev is not None:
+            ms_icp = event_ms(lambda: solver.run(pd, prev_dev[0], prev_dev[1], settings.schedule))
+        et, er = pose_error(out["pose"], truth)
+        rt, rr = pose_error(ref_pose, truth)
+        dt, dr = pose_error(out["pose"], ref_pose)
+        frames.append(dict(frame=i, n_points=out["n_points"], iterations=out["iterations"], reference_iterations=ref_it,
+                           fitness=out["fitness"], rmse=out["rmse"], err_mm=et * 1e3, err_deg=er,
+                           reference_err_mm=rt * 1e3, reference_err_deg=rr, gpu_vs_reference_mm=dt * 1e3,
+                           gpu_vs_reference_deg=dr, normals_ms=ms_nrm, icp_schedule_ms=ms_icp,
+                           track_wall_ms=wall_gpu * 1e3, reference_normals_ms=t_nrm * 1e3,
+                           reference_icp_ms=t_icp * 1e3))
+        print(f"frame {i}: {out['n_points']} points, iterations {out['iterations']}, error {et * 1e3:.3f} mm "
+              f"{er:.4f} deg (reference {rt * 1e3:.3f} mm {rr:.4f} deg, GPU vs reference {dt * 1e3:.4f} mm "
+              f"{dr:.5f} deg); normals {ms_nrm:.3f} ms, schedule {ms_icp:.3f} ms (reference: normals "
+              f"{t_nrm * 1e3:.1f} ms, schedule {t_icp * 1e3:.1f} ms)", flush=True)
+        prev, prev_dev = (pts.numpy(), nrm), (pd, nd)
+    tracked = frames[1:]
+    rec = dict(kind=args.kind, scans=args.scans, target_points=args.points,
+               path_length_m=float(sum(np.linalg.norm(step_pose(i)[:3, 3]) for i in range(args.scans - 1))),
+               final_drift_mm=frames[-1]["err_mm"], final_drift_deg=frames[-1]["err_deg"],
+               reference_final_drift_mm=frames[-1]["reference_err_mm"],
+               reference_final_drift_deg=frames[-1]["reference_err_deg"],
+               gpu_vs_reference_final_mm=frames[-1]["gpu_vs_reference_mm"],
+               gpu_vs_reference_final_deg=frames[-1]["gpu_vs_reference_deg"],
+               normals_ms_median=float(np.median([f["normals_ms"] for f in frames])),
+               icp_schedule_ms_median=float(np.median([f["icp_schedule_ms"] for f in tracked])) if tracked else 0.0,
+               reference_normals_ms_median=float(np.median([f["reference_normals_ms"] for f in frames])),
+               reference_icp_ms_median=float(np.median([f["reference_icp_ms"] for f in tracked])) if tracked else 0.0,
+               device=torch.cuda.get_device_name(0), frames=frames)
+    print(json.dumps({k: v for k, v in rec.items() if k != "frames"}), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            f.write(json.dumps(rec, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
