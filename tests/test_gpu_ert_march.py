@@ -265,7 +265,7 @@ def test_march_step_bitwise_on_trained_field(trained):
             torch.cuda.synchronize()
             if ert:
                 assert eng.ert_bounds() == plan
-                assert eng._ert_marched == (1 if march else None)
+                assert eng.planner.marched == (1 if march else None)
             alive.append(eng.ert_alive_last())
         eng.finish()
         torch.cuda.synchronize()

@@ -132,9 +132,10 @@ def test_ert_auto_plans_from_termination_counts(trained, monkeypatch):
     without a host sync; on the trained field it picks phases, every ray is counted once per step, and the steps
     stay bitwise those without termination; on a fresh field (no ray terminates) it picks none.  (This batch,
     2048 rays, is too small for the fitted fixed costs to let phases pay: the test lowers them.)"""
+    from loner_amd import ert as E_
     from loner_amd import step as S_
-    monkeypatch.setattr(S_, "ERT_FIXED_US", 2.0)
-    monkeypatch.setattr(S_, "ERT_PHASE_US", 2.0)
+    monkeypatch.setattr(E_, "ERT_FIXED_US", 2.0)  # (the module where the planner's cost model looks them up)
+    monkeypatch.setattr(E_, "ERT_PHASE_US", 2.0)
     cfg, sd, window, g = trained
     outs = []
     for mode in (False, "auto"):
@@ -172,11 +173,12 @@ def test_ert_auto_plans_from_termination_counts(trained, monkeypatch):
 def test_ert_plan_change_waits_for_window(trained, monkeypatch):
     """LONER_ERT=auto under HIP-graph replay: the first plan is taken at once, a later one waits for the window's
     end (release()), where the graphs are captured anew anyway, instead of an eager step and a capture mid-window."""
+    from loner_amd import ert as E_
     from loner_amd import step as S_
     cfg, sd, window, g = trained
     plans = [[0, S // 2, S], [0, S // 4, S // 2, S]]
     pick = [plans[0]]
-    monkeypatch.setattr(S_, "ert_plan", lambda *a, **k: list(pick[0]))
+    monkeypatch.setattr(E_, "ert_plan", lambda *a, **k: list(pick[0]))  # (where ErtPlanner.observe looks it up)
     st = S_.FieldState(cfg, device="cuda")
     st.load_state_dict(sd)
     st.reset_optimizer()
@@ -190,7 +192,7 @@ def test_ert_plan_change_waits_for_window(trained, monkeypatch):
     for k in range(3, 8):
         eng.step_window(window, global_step=g + k, iteration_idx=k)
         torch.cuda.synchronize()
-    assert eng.ert_bounds() == plans[0] and eng._ert_next[0] == plans[1]
+    assert eng.ert_bounds() == plans[0] and eng.planner.next[0] == plans[1]
     eng.finish()
     eng.release()
     assert eng.ert_bounds() == plans[1]

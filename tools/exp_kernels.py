@@ -44,7 +44,7 @@ def main():
     R = rays.shape[0]
     cfg = S_.StepConfig(n_samples=n_samples, loss=S_.LossConfig.from_dict(bench.LOSS_PRESETS[preset]))
     st = S_.FieldState(cfg, device=dev)
-    eng = S_.StepEngine(st, R, seed=1, count_in_forward=os.environ.get("EXP_FWD_COUNT", "1") == "1")
+    eng = S_.StepEngine(st, R, seed=1)
     scale = syn.CUBES[kind][0]
     far = float(rays[0, -1])
     for i in range(3):
@@ -64,7 +64,7 @@ def main():
     for i in range(steps):  # forward without histogram, then count + full backward
         L.call("lnr_hashgrid_fwd_rays", L.ctypes.byref(st.desc), rays, eng.z, R, n_samples, st.table_f16, eng.enc, N,
                None, 0, s)
-        eng._grid_bwd(rays, R, n_samples, N, 0, s)
+        eng._grid_bwd(rays, R, 0, s)
     torch.cuda.synchronize()
     print(f"{cfg_name}: {ms:.3f} ms/step (no OGM), {R * n_samples / ms * 1e3:.3e} ray-samples/s", flush=True)
 

@@ -67,7 +67,7 @@ def main():
 
         def scatter():
             hist.copy_(snap)
-            e._grid_bwd(e.rays, R, S, N, L.BWD_COUNTS_READY | L.BWD_LEVEL_MAX_READY | L.BWD_NO_ACCUM, L.stream(dev))
+            e._grid_bwd(e.rays, R, L.BWD_COUNTS_READY | L.BWD_LEVEL_MAX_READY | L.BWD_NO_ACCUM, L.stream(dev))
 
         def accum():
             L.call("lnr_hashgrid_bwd_accum", L.ctypes.byref(st.desc), R * S, e.bwd_ws, e.bwd_ws_bytes, 0,

@@ -62,7 +62,7 @@ def main():
                    e.depth, e.opacity, None, e.level_max_ptr, e.d_jac, L.stream(dev))
 
         def scatter():
-            e._grid_bwd(e.rays, R, S, N, L.BWD_COUNTS_READY | L.BWD_LEVEL_MAX_READY | L.BWD_NO_ACCUM, L.stream(dev))
+            e._grid_bwd(e.rays, R, L.BWD_COUNTS_READY | L.BWD_LEVEL_MAX_READY | L.BWD_NO_ACCUM, L.stream(dev))
 
         # the scan turns the encode's histogram into offsets in place: a scatter timed on its own (no encode before
         # it) first restores the encode's counts (a ~10 us copy, in the alone times only)

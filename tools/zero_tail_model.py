@@ -1,4 +1,4 @@
-"""Modelled exposure of the sharded optimiser's tail (StepEngine._step_zero) per level cut, for one rank of an
+"""Modelled exposure of the sharded optimiser's tail (StepEngine._bwd_adam_sharded) per level cut, for one rank of an
 N-GPU step.  Inputs: the measured accumulate time of each level range at that rank's
 batch (tools/bwd_levels.py C4 s8 <ranges> --json, profiles/r05_bwd_levels_C4s8.json), the Adam pass rate
 (k_adam streams 32 B per parameter at ~7 TB/s), and a ring bandwidth B and per-collective
