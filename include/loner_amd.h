@@ -28,6 +28,9 @@
  *   lnr_build_lidar_rays          per-step ray selection (RANDOM / MASK / sky) + KeyFrame.build_lidar_rays
  *                                 src/mapping/optimizer.py:363-424, src/mapping/keyframe.py:75-105,
  *                                 src/common/ray_utils.py:31-60,269-322
+ *   lnr_cloud_cell_keys / lnr_voxel_heads / lnr_voxel_reduce / lnr_nn_search / lnr_dist_stats
+ *                                 Open3D's voxel_down_sample and compute_point_cloud_distance, and the metric sums
+ *                                 analysis/evaluate_lidar_map.py:16-81, analysis/renderer_lidar.py:292-349
  *
  * Conventions:
  *   - all data pointers are DEVICE pointers owned by the caller (PyTorch); no allocation, no host
@@ -697,6 +700,64 @@ int lnr_icp_init(lnr_icp_state* state, const double* T0, void* stream);
 int lnr_icp_stage(const float* src, int64_t n_src, const float* tgt, const float* tgt_normals, int64_t n_tgt,
                   float threshold, int32_t max_iterations, double rel_fitness, double rel_rmse, lnr_icp_state* state,
                   void* workspace, int64_t ws_bytes, int32_t* corr_idx, float* corr_d2, void* stream);
+
+/* ---------------------------------------------------------------- map evaluation (analysis/evaluate_lidar_map.py) */
+/* Voxel filter, nearest-neighbour distances and their statistics: what the reference's map evaluation hands to Open3D
+ * (voxel_down_sample, compute_point_cloud_distance).  Sorting and prefix sums between the calls are the caller's
+ * (a STABLE sort of the keys; loner_amd/map_eval.py).  No float atomics; every result repeats bit for bit. */
+#define LNR_CLOUD_MAX_POINTS (1 << 27)
+#define LNR_CLOUD_CELL_BITS 21              /* cell indices per axis: [0, 2^21) */
+#define LNR_CLOUD_BAD_KEY INT64_MAX         /* the key of a point without a cell: the largest one */
+#define LNR_CLOUD_NONFINITE 1u              /* status: a coordinate was nan or inf */
+#define LNR_CLOUD_GRID_RANGE 2u             /* status: a cell index fell outside [0, 2^21) */
+#define LNR_CLOUD_VOXEL_CHUNK 64            /* points per partial sum of the voxel filter */
+#define LNR_NN_MAX_RINGS 4                  /* rings a query expands before it joins the exhaustive scan */
+/* keys[i] = ix << 42 | iy << 21 | iz of pts (n, 3), i_a = floor((double(p_a) - origin[a]) / cell) with an IEEE fp64
+ * subtraction and division.  origin: 3 DEVICE doubles.  A non-finite coordinate ORs LNR_CLOUD_NONFINITE into *status
+ * (1 device uint32, never cleared here), an index outside [0, 2^21) (a non-finite origin included) LNR_CLOUD_GRID_RANGE;
+ * such a point gets LNR_CLOUD_BAD_KEY.  No entry point below uses a key as an index: keys are only compared.
+ * 1 <= n <= LNR_CLOUD_MAX_POINTS, 1e-12 <= cell < inf. */
+int lnr_cloud_cell_keys(const float* pts, int64_t n, const double* origin, double cell, int64_t* keys,
+                        uint32_t* status, void* stream);
+/* heads[i] = 1 where sorted_keys[i] starts a run of equal keys (i = 0, or a key unlike its predecessor's), else 0.
+ * The inclusive scan of heads numbers the occupied voxels in ascending key order from 1. */
+int lnr_voxel_heads(const int64_t* sorted_keys, int64_t n, int32_t* heads, void* stream);
+/* 0 for sizes outside 1 <= n_vox <= n <= LNR_CLOUD_MAX_POINTS. */
+int64_t lnr_voxel_workspace_bytes(int64_t n, int64_t n_vox);
+/* Open3D's voxel_down_sample from the sorted order: perm[i] (int64) is the point at sorted position i, head_scan[i]
+ * (int64) the inclusive scan of lnr_voxel_heads, n_vox its last entry.  means (n_vox, 3) fp32: the mean of each
+ * voxel's points, summed in fp64 and rounded once; counts (n_vox int32) when not NULL; both in ascending key order
+ * (Open3D's own order is that of an unordered map).  A voxel's points are cut, in sorted order, into chunks of
+ * LNR_CLOUD_VOXEL_CHUNK; one thread sums a chunk front to back and the voxel's chunk sums are added in chunk order:
+ * the order of every sum depends on the data alone, and a stable sort makes it the points' input order.  Entries of
+ * perm outside [0, n) and of head_scan outside [1, n_vox] are skipped, never followed.  workspace:
+ * lnr_voxel_workspace_bytes(n, n_vox) bytes, 8-byte aligned. */
+int lnr_voxel_reduce(const float* pts, const int64_t* perm, const int64_t* head_scan, int64_t n, int64_t n_vox,
+                     void* workspace, int64_t ws_bytes, float* means, int32_t* counts, void* stream);
+/* Open3D's compute_point_cloud_distance: for each point of src (n_src, 3) the target point with the smallest
+ * (d2, index), d2 = dx dx + dy dy + dz dz in fp32 with every operation rounded (no contraction), so ties go to the
+ * lower index.  The target comes as a uniform grid: tgt_sorted (n_tgt, 3) in ascending key order, tgt_keys their
+ * lnr_cloud_cell_keys for (origin, cell), tgt_perm (int32) each one's index in the caller's order; dims: 3 DEVICE
+ * int32, the grid's cells per axis (every target cell index < dims[a] <= 2^21).  Outputs: idx (int32, the caller's
+ * index), d2 (fp32, the search key), dist (fp64: sqrt of the fp64 squared distance to the winner, recomputed).
+ * A query expands Chebyshev rings of cells around its own (signed: it may lie outside the box; rings are cut to the
+ * box, empty ones skipped) and stops after ring r >= 1 once d2 <= (r cell)^2 (1 - 2^-20), or when the box is
+ * covered; after LNR_NN_MAX_RINGS rings, or at a ring of more than 81 columns, it joins a list in the workspace (an
+ * integer counter; the list's order is arbitrary and no result depends on it) and is answered by an exhaustive scan
+ * of the target with the same key.  Either way the result is the exact minimum of the key over all targets,
+ * whatever `cell` is.  A non-finite query ORs LNR_CLOUD_NONFINITE into *status and gets idx -1, d2 = dist = inf.
+ * 1 <= n_src, n_tgt <= LNR_CLOUD_MAX_POINTS, cell as above.  workspace: lnr_nn_workspace_bytes(n_src) bytes (0 for
+ * an n_src outside the limits), 8-byte aligned. */
+int64_t lnr_nn_workspace_bytes(int64_t n_src);
+int lnr_nn_search(const float* src, int64_t n_src, const float* tgt_sorted, const int64_t* tgt_keys,
+                  const int32_t* tgt_perm, int64_t n_tgt, const double* origin, double cell, const int32_t* dims,
+                  void* workspace, int64_t ws_bytes, int32_t* idx, float* d2, double* dist, uint32_t* status,
+                  void* stream);
+/* out[0] = sum of dist[0 .. n), out[1] = the number of entries > threshold (as a double), fp64: one row of partial
+ * sums per 4096 entries in the workspace, the rows added in a fixed order.  0 for n outside [1, LNR_CLOUD_MAX_POINTS]. */
+int64_t lnr_dist_stats_workspace_bytes(int64_t n);
+int lnr_dist_stats(const double* dist, int64_t n, double threshold, void* workspace, int64_t ws_bytes, double* out,
+                   void* stream);
 
 /* ---------------------------------------------------------------- utilities */
 /* dst[i] = lo + (hi-lo) * U(splitmix64(((uint64)seed << 32) + start + i)) */

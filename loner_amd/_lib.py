@@ -86,6 +86,11 @@ ERT_T_MIN = 1e-50  # LNR_ERT_T_MIN
 STATUS_NAN_LOSS, STATUS_INF_LOSS, STATUS_SIGMA_CLIPPED, STATUS_NONFINITE_OUTPUT = 1, 2, 4, 8
 
 
+CLOUD_NONFINITE, CLOUD_GRID_RANGE = 1, 2  # LNR_CLOUD_* status bits
+CLOUD_BAD_KEY = 2 ** 63 - 1
+CLOUD_CELL_BITS = 21
+CLOUD_VOXEL_CHUNK = 64
+
 SELECT = {"RANDOM": 0, "MASK": 1, "ALL": 2, "GIVEN": 3}
 
 
@@ -225,6 +230,15 @@ _SIGNATURES = {
     "lnr_icp_init": (ctypes.c_int, [c_p, ctypes.POINTER(c_d), c_p]),
     "lnr_icp_stage": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_f, c_i32, c_d, c_d, c_p, c_p, c_i64, c_p, c_p,
                                      c_p]),
+    "lnr_cloud_cell_keys": (ctypes.c_int, [c_p, c_i64, c_p, c_d, c_p, c_p, c_p]),
+    "lnr_voxel_heads": (ctypes.c_int, [c_p, c_i64, c_p, c_p]),
+    "lnr_voxel_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "lnr_voxel_reduce": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "lnr_nn_workspace_bytes": (c_i64, [c_i64]),
+    "lnr_nn_search": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_d, c_p, c_p, c_i64, c_p, c_p, c_p, c_p,
+                                     c_p]),
+    "lnr_dist_stats_workspace_bytes": (c_i64, [c_i64]),
+    "lnr_dist_stats": (ctypes.c_int, [c_p, c_i64, c_d, c_p, c_i64, c_p, c_p]),
     "lnr_fill_uniform": (ctypes.c_int, [c_p, c_i64, c_u32, c_f, c_f, c_i64, c_p]),
     "lnr_f32_to_f16": (ctypes.c_int, [c_p, c_p, c_i64, c_p]),
 }
