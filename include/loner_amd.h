@@ -449,9 +449,10 @@ int lnr_pose_grad(const float* rays, const float* z, const float* d_pos, const f
 /* The poses' Adam step (torch.optim.Adam, the pose group of optimizer.py:262: betas, eps, lr = lrate_pose x the
  * ExponentialLR factor; step = this Adam's step count, from 1) on pose6 with moments m, v (K, 6), for keyframes
  * with optimise[k] != 0 (NULL: all), then rows (K, 12) = [R | t] of every pose (the RayWindow's pose layout; may
- * be NULL).  grad NULL: only the rows are written (m, v, step unused). */
+ * be NULL).  grad NULL: only the rows are written (m, v, step unused).  The hyper-parameters are doubles, as
+ * lnr_adam_step's: 1 - beta is formed in double before its rounding to fp32. */
 int lnr_pose_adam(float* pose6, float* m, float* v, const float* grad, const uint8_t* optimise, int32_t n_kf,
-                  int64_t step, float lr, float beta1, float beta2, float eps, float* rows, void* stream);
+                  int64_t step, double lr, double beta1, double beta2, double eps, float* rows, void* stream);
 /* Forward-only render from enc (inference path, C3 shape): sigma MLP + compositing.  With weights
  * (R,S) given, the sigma MLP runs tile-parallel first and stages sigma in weights, which the
  * compositing then overwrites with the weights (weights must not alias the other buffers); without,

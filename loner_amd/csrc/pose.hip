@@ -257,14 +257,16 @@ extern "C" int lnr_pose_grad(const float* rays, const float* z, const float* d_p
 }
 
 extern "C" int lnr_pose_adam(float* pose6, float* m, float* v, const float* grad, const uint8_t* optimise,
-                             int32_t n_kf, int64_t step, float lr, float beta1, float beta2, float eps, float* rows,
+                             int32_t n_kf, int64_t step, double lr, double beta1, double beta2, double eps, float* rows,
                              void* stream) {
   LNR_REQUIRE(n_kf > 0 && (step >= 1 || grad == nullptr), "lnr_pose_adam: bad sizes");
   LNR_REQUIRE(pose6 && (grad == nullptr || (m && v)) && (grad || rows), "lnr_pose_adam: null pointer");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  // the hyper-parameters arrive as doubles and every derived scalar is formed in double before its single rounding
+  // to fp32, as torch.optim.Adam forms them and as lnr_adam_step does (1 - beta2 from the float 0.999f is 1.3e-5 off)
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
   hipLaunchKernelGGL(k_pose_adam, dim3((unsigned)((n_kf + 63) / 64)), dim3(64), 0, as_stream(stream), pose6, m, v, grad,
-                     optimise, n_kf, 1.0f - beta1, beta2, 1.0f - beta2, (float)((double)lr / bc1), (float)sqrt(bc2), eps,
-                     rows);
+                     optimise, n_kf, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1),
+                     (float)sqrt(bc2), (float)eps, rows);
   LNR_RETURN_LAUNCH("lnr_pose_adam");
 }

@@ -66,3 +66,79 @@ def test_sky_rays_vs_oracle(P, kind):
         dots = got.T @ ref
         assert np.mean(dots.max(1) > 1 - 1e-6) > 0.99 and np.mean(dots.max(0) > 1 - 1e-6) > 0.99
         assert np.allclose(np.linalg.norm(got, axis=0), 1, atol=1e-5)
+
+
+# ------------------------------------------------------------------ exact cases (tests/kernel_cases.py)
+def _sky_call(dirs, pose, cap=None, guard=8):
+    """lnr_sky_rays through the C ABI: (count, out (cap + guard, 3) prefilled with NaN)."""
+    from loner_amd import _lib as L
+    d = torch.from_numpy(np.ascontiguousarray(dirs.T)).cuda()
+    sp = L.SkyParams()
+    for i in range(9):
+        sp.rot[i] = float(np.asarray(pose)[:3, :3].reshape(-1)[i])
+    sp.top_rows, sp.horizon_deg = 3, 10.0
+    cap = int(L.lib().lnr_sky_rays_capacity()) if cap is None else cap
+    out = torch.full((cap + guard, 3), float("nan"), dtype=torch.float32, device="cuda")
+    cnt = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    L.call("lnr_sky_rays", d, d.shape[0], L.ctypes.byref(sp), out, cap, cnt, L.stream())
+    torch.cuda.synchronize()
+    return int(cnt.item()), out.cpu().numpy()
+
+
+@pytest.mark.parametrize("case", ["full", "partial"])
+def test_sky_rays_exact(P, case):
+    """A scan built from chosen integer bins, each direction at its bin's centre (fp32 atan2 cannot flip the
+    rounding): theta = -180 and 180 (the == 360 -> 0 wrap) or part of the azimuth (theta.min() > -180), phi.min() > 0,
+    single-bin holes (closed), 3 x 3 holes (kept), holes at each image border, the forced top rows, a tilted pose.
+    The count equals the oracle's and the directions match it in order (both row-major) to 1e-6; no candidate is
+    within 1e-3 degrees of the horizon threshold (tests/test_kernel_cases_ref.py)."""
+    import kernel_cases as C
+    dirs, _ = C.sky_scan(case)
+    ref = opre.sky_rays(dirs, C.SKY_POSE[:3, :3])
+    n, out = _sky_call(dirs, C.SKY_POSE)
+    assert n == ref.shape[1], (n, ref.shape)
+    np.testing.assert_allclose(out[:n], ref.T, atol=1e-6, rtol=0)
+    assert np.all(np.isnan(out[n:]))
+    got = P.sky_rays(torch.from_numpy(np.ascontiguousarray(dirs.T)).cuda(), C.SKY_POSE).cpu().numpy()
+    np.testing.assert_array_equal(got, out[:n])
+    # cap below the count: the count is still the total, and nothing is written past cap
+    cap = n // 2
+    n2, out2 = _sky_call(dirs, C.SKY_POSE, cap=cap)
+    assert n2 == n
+    np.testing.assert_array_equal(out2[:cap], out[:cap])
+    assert np.all(np.isnan(out2[cap:]))
+
+
+def test_sky_rays_one_point(P):
+    """A one-point scan: a one-row image, forced occupied by the top rows: no sky rays."""
+    import kernel_cases as C
+    dirs = C.bin_directions([30], [60])
+    assert opre.sky_rays(dirs, C.SKY_POSE[:3, :3]).shape[1] == 0
+    n, out = _sky_call(dirs, C.SKY_POSE)
+    assert n == 0 and np.all(np.isnan(out))
+    assert P.sky_rays(torch.from_numpy(np.ascontiguousarray(dirs.T)).cuda(), C.SKY_POSE).shape == (0, 3)
+
+
+@pytest.mark.parametrize("name", ["general", "identity_rotation", "near_pi"])
+def test_motion_compensate_every_point(P, name):
+    """Every point of n = 1000 (no multiple of the 256-thread block) against the vectorised float64 restatement of
+    the oracle (kernel_cases.motion_compensate_vec, equal to the per-point oracle: tests/test_kernel_cases_ref.py),
+    at the tolerances of test_motion_compensate_vs_oracle: timestamps below t0 and above t1 (extrapolation), a
+    target pose that is neither end, equal rotations with a translation (the identity flag), a relative rotation
+    of pi - 1e-3."""
+    import kernel_cases as C
+    c = C.motion_case(name)
+    d_dev = torch.from_numpy(c["dirs"].T.astype(np.float32)).cuda().contiguous()
+    r_dev = torch.from_numpy(c["dists"].astype(np.float32)).cuda()
+    t_dev = torch.from_numpy(c["ts"].astype(np.float32)).cuda()
+    mc = P.motion_comp_params(c["start"], c["end"], c["t"][0], c["t"][1], c["target"])
+    assert mc.identity == (1 if name == "identity_rotation" else 0)
+    P.motion_compensate(d_dev, r_dev, t_dev, (c["start"], c["end"]), c["t"], c["target"])
+    torch.cuda.synchronize()
+    od, orr = C.motion_compensate_vec(c["dirs"], c["dists"], c["ts"], c["start"], c["end"], c["t"][0], c["t"][1],
+                                      c["target"])
+    got_d, got_r = d_dev.cpu().numpy().T, r_dev.cpu().numpy()
+    print(f"motion {name}: worst |ddir| {np.abs(got_d - od).max():.2e}, worst |ddist| / dist "
+          f"{(np.abs(got_r - orr) / orr).max():.2e}")
+    np.testing.assert_allclose(got_d, od, atol=2e-5)
+    np.testing.assert_allclose(got_r, orr, rtol=2e-5, atol=2e-5)
