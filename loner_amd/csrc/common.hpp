@@ -115,32 +115,24 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 // ------------------------------------------------------------------ wave / block reductions
-// The butterfly over lane distances 32, 16, 8, 4, 2, 1 (every lane ends with the total).  LNR_WAVE_RED_DPP: the
+// The butterfly over lane distances 32, 16, 8, 4, 2, 1 (every lane ends with the total), its
 // exchanges without LDS permutes: v_permlane32_swap / v_permlane16_swap (gfx950) for 32 and 16, DPP row_ror:8
 // for 8 (within a row, lane p + 8 mod 16 = p ^ 8), row_ror:4 for 4 (lane p + 4 mod 16 holds the same value as
 // p ^ 4 once the 8-apart lanes are equal), quad_perm for 2 and 1.  Each lane adds the same two values as the
 // __shfl_xor butterfly (operands at most swapped): bitwise the same sums (tools/ubench/ubench_permlane.hip; C2 loss
 // bit-identical, field stage 0.244-0.246 -> 0.242 ms).
-#ifndef LNR_WAVE_RED_DPP
-#define LNR_WAVE_RED_DPP 1
-#endif
 template <class Op>
 __device__ __forceinline__ float wave_butterfly(float v, Op op) {
-  if (LNR_WAVE_RED_DPP) {
-    const uint32_t b = __float_as_uint(v);
-    const auto r32 = __builtin_amdgcn_permlane32_swap(b, b, false, false);  // {lanes 0-31, lanes 32-63} in both halves
-    v = op(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-    const uint32_t c = __float_as_uint(v);
-    const auto r16 = __builtin_amdgcn_permlane16_swap(c, c, false, false);  // {even row, odd row} of each row pair
-    v = op(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-    v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, false)));  // row_ror:8
-    v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xF, 0xF, false)));  // row_ror:4
-    v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));   // quad [2,3,0,1]
-    v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)));   // quad [1,0,3,2]
-    return v;
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+  const uint32_t b = __float_as_uint(v);
+  const auto r32 = __builtin_amdgcn_permlane32_swap(b, b, false, false);  // {lanes 0-31, lanes 32-63} in both halves
+  v = op(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
+  const uint32_t c = __float_as_uint(v);
+  const auto r16 = __builtin_amdgcn_permlane16_swap(c, c, false, false);  // {even row, odd row} of each row pair
+  v = op(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
+  v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, false)));  // row_ror:8
+  v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xF, 0xF, false)));  // row_ror:4
+  v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));   // quad [2,3,0,1]
+  v = op(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)));   // quad [1,0,3,2]
   return v;
 }
 __device__ __forceinline__ float wave_sum(float v) {
@@ -233,9 +225,6 @@ __device__ __forceinline__ unsigned long long stamp() {
 // OccupancyGridModel.interpolate (src/models/model_tcnn.py:126-134): grid_sample of the (R, R, R) grid
 // at (x, y, z) in [-1, 1] (x the fastest axis), trilinear, align_corners=False, zeros padding.  Its
 // corner order and weights are those of the grid-gradient splat (optim.hip).
-#ifndef LNR_OCC_PAIR
-#define LNR_OCC_PAIR 1
-#endif
 __device__ __forceinline__ float occ_grid_sample(const float* __restrict__ occ, int R, float x, float y, float z) {
   const float ix = ((x + 1.f) * (float)R - 1.f) / 2.f;
   const float iy = ((y + 1.f) * (float)R - 1.f) / 2.f;
@@ -246,7 +235,6 @@ __device__ __forceinline__ float occ_grid_sample(const float* __restrict__ occ, 
   const float wy[2] = {(float)(y0 + 1) - iy, iy - (float)y0};
   const float wz[2] = {(float)(z0 + 1) - iz, iz - (float)z0};
   float acc = 0.f;
-#if LNR_OCC_PAIR
   // The two x-corners of each y/z edge are adjacent floats: one 8-B load per edge (4 gathers, not 8), from
   // x0 clamped to [0, R - 2] so that a pair with one corner outside the grid reads the other one.  The same
   // products added in the same order (a corner outside adds nothing, as before): bitwise the 8-load form.
@@ -268,9 +256,8 @@ __device__ __forceinline__ float occ_grid_sample(const float* __restrict__ occ, 
     }
     return acc;
   }
-#endif
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
+  for (int c = 0; c < 8; ++c) {  // (R < 2: no pair to read)
     const int bx = c & 1, by = (c >> 1) & 1, bz = (c >> 2) & 1;
     const int cx = x0 + bx, cy = y0 + by, cz = z0 + bz;
     const float w = wx[bx] * wy[by] * wz[bz];

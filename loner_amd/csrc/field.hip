@@ -559,9 +559,6 @@ constexpr int kWavesPerBlock = NT / 64;
 #define LNR_MLP_BWD_BLOCKS 512  // workgroups of k_mlp_bwd_tiles (and dW slabs), at most: one resident round (C2: 178.8 + 7.7 us slab reduce at 1024, 175.5 + 4.9 at 512)
 #endif
 constexpr int kMlpBwdBlocks = LNR_MLP_BWD_BLOCKS;
-#ifndef LNR_FIELD_SPLIT
-#define LNR_FIELD_SPLIT 1  // lnr_field_train: MLP forward and compositing as two kernels (k_sigma_fwd_tiles, k_composite_wave)
-#endif
 constexpr int kSigmaLevels = 16;  // the sigma MLP's 32 inputs: 16 levels x 2 features
 
 __device__ __forceinline__ double wave_excl_prod(double p) {
@@ -787,36 +784,8 @@ __device__ void composite_loss_wave(const FieldArgs& a, float* sig, int64_t r) {
   }
 }
 
-// Phase 1, one wave per ray: sigma MLP forward -> compositing -> loss -> compositing backward;
-// writes dL/dsigma (R, S) fp32 for phase 2.
-template <int C>
-__global__ void __launch_bounds__(NT) k_field_wave(FieldArgs a) {
-  if (a.denc_max && blockIdx.x == 0 && threadIdx.x < kSigmaLevels) a.denc_max[threadIdx.x] = 0.f;  // before k_mlp_bwd_tiles
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
-  constexpr int S = 64 * C;  // == a.S (checked at launch)
-  float* sig = reinterpret_cast<float*>(smem) + wid * S;  // this wave's ray: sigma, then dL/dsigma
-  SigmaWeights sw;
-  load_sigma_weights(a.w, sw);
-  for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + wid; r < a.n_rays; r += (int64_t)gridDim.x * kWavesPerBlock) {
-#pragma unroll 8
-    for (int tb = 0; tb < S; tb += 16) {
-      SigmaHidden h;
-      const float sgm = sigma_tile_fwd(sw, load_enc_operand(a.enc, a.enc_stride, r * S + tb + c, true), h);
-      if (g == 0) sig[tb + c] = sigma_to_f16(sgm);
-      if (a.lp.dev_status && __any(!isfinite(round_f16(sgm))) && lane == 0) atomicOr(a.lp.dev_status, LNR_STATUS_SIGMA_CLIPPED);
-    }
-    wave_lds_handoff();
-    composite_loss_wave<C>(a, sig, r);
-    wave_lds_handoff();
-#pragma unroll
-    for (int k = 0; k < C; ++k) a.d_sigma[r * S + 64 * k + lane] = sig[64 * k + lane];  // coalesced
-    wave_lds_handoff();  // sig is rewritten by the next ray
-  }
-}
-
-// The same phase split in two, so neither kernel carries the other's registers (k_field_wave<8>: 211
-// registers, 2 waves per SIMD, its encoding loads exposed between rays).
+// Phase 1 (sigma MLP forward -> compositing -> loss -> compositing backward; writes dL/dsigma (R, S) fp32 for
+// phase 2) is two kernels, so neither carries the other's registers (retired variants: the fused form).
 // Phase 1a, tile-parallel: sigma MLP forward over 64-sample units (4 tiles per wave trip, every load
 // first), sigma (fp16-rounded, as tcnn returns it) into a.d_sigma.
 constexpr int kSigmaFwdUnit = 64;
@@ -996,7 +965,7 @@ constexpr int kMarchPitch = 68;  // words per level of the LDS image: lanes 16 g
                            // wave at 6 waves (80 VGPRs) and with four at 5 waves (96): neither latency nor occupancy
                            // bounds it, the 16-level gather working set does
 #endif
-// The forward's sigma weights kept in LDS ([operand][64 lanes] of 16 B, as SigmaWeightsLds; 6 KB per workgroup):
+// The forward's sigma weights kept in LDS ([operand][64 lanes] of 16 B: conflict-free ds_read_b128; 6 KB per workgroup):
 // layer 0's four A operands and the output layer's two, read where used instead of held in 24 registers (with
 // them in registers the kernel takes 96 VGPRs, 5 waves per SIMD; from LDS 64 and 8, no scratch either way).
 struct MarchWeightsLds {
@@ -1149,12 +1118,12 @@ __device__ __forceinline__ uint32_t pack_h2(float x, float y) {
   return __builtin_bit_cast(uint32_t, h);
 }
 
-// Packed-half pair for k_mlp_bwd_tiles (LNR_MLP_PK): the hidden layer kept as 8 fp16-pair words per tile
+// Packed-half pair for k_mlp_bwd_tiles: the hidden layer kept as 8 fp16-pair words per tile
 // (v_cvt_pk + v_pk_max: the ReLU of the rounded value), the ReLU masks taken from those words by integer ops
 // (pk_nonzero_mask), and dW0's operands staged as [sample][neuron] rows of 8-byte chunks read back transposed
-// (ds_read_b64_tr_b16) instead of one 2-byte LDS store per value.  Same operands at the same MFMA k
-// positions as dw0_pair_mfma (the k order matters: tools/ubench/ubench_mfma_korder.hip), bitwise the same sums
-// except where the scaled ds * Enc operand rounds a tie differently (below).
+// (ds_read_b64_tr_b16) instead of one 2-byte LDS store per value.  Sample s of the pair sits at the MFMA's
+// k position s (the k order matters to the sum's bits: tools/ubench/ubench_mfma_korder.hip); DESIGN.md's
+// retired variants tell how the sums compare with the per-value staging this replaced.
 // Wave image of a pair: the ReLU mask (1.0 / 0.0), 32 sample rows x 16 chunks (64 hid), and ds * Enc at the
 // pair's scale, 32 rows x 8 chunks (32 inputs).  Chunk swizzles (MI355X_MICROARCH.md LDS table: stores bank
 // on (a/4) mod 32 in 16-lane groups for b64 and 8-lane groups for b128, the transposed reads on (a/4) mod 64 in
@@ -1193,18 +1162,6 @@ __device__ __forceinline__ float enc_absmax(const uint32_t (&x)[4]) {
 // Phase 2, tile-parallel: sigma MLP backward over 32-sample tile pairs (no per-ray structure):
 // d_enc (level-major float2) and the per-block dW slab.
 // (2 waves per SIMD at its 242 VGPRs; forcing 3 or 4 spills 45 / 116 VGPRs: 0.18 -> 0.56 / 0.76 ms)
-#ifndef LNR_MLP_PREFETCH
-#define LNR_MLP_PREFETCH 1  // tile pairs loaded ahead in k_mlp_bwd_tiles (1 or 2; C2: 271 against 279 us)
-#endif
-#ifndef LNR_MLP_W_LDS
-#define LNR_MLP_W_LDS 0  // the layer-0 weight operands in LDS instead of registers (k_mlp_bwd_tiles)
-#endif
-#ifndef LNR_MLP_SPLIT_PAIR
-#define LNR_MLP_SPLIT_PAIR 0  // k_mlp_bwd_tiles: one tile of the pair live at a time (pair_split)
-#endif
-#ifndef LNR_MLP_PK
-#define LNR_MLP_PK 1  // k_mlp_bwd_tiles: the packed-half pair (pair_pk)
-#endif
 #ifndef LNR_MLP_BWD_WAVES
 #define LNR_MLP_BWD_WAVES 2  // waves per SIMD (3 spills 113 registers with the weights in registers)
 #endif
@@ -1213,18 +1170,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MLP
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   _Float16* lds = reinterpret_cast<_Float16*>(smem) + wid * (64 * 32 + 32 * 32);
-#if LNR_MLP_W_LDS
-  SigmaWeightsLds sw;
-  {
-    SigmaWeights swr;
-    load_sigma_weights(a.w, swr);
-    sw.stage(reinterpret_cast<half8_t*>(reinterpret_cast<_Float16*>(smem) + kWavesPerBlock * (64 * 32 + 32 * 32)), swr);
-  }
-  __syncthreads();
-#else
   SigmaWeights sw;
   load_sigma_weights(a.w, sw);
-#endif
   DW0Mfma acc;
   acc.init();
   float dw1[16];
@@ -1233,10 +1180,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MLP
   float2* denc = reinterpret_cast<float2*>(a.d_enc);
   float lmax[4] = {0.f, 0.f, 0.f, 0.f};  // max |d_enc| of this lane's levels 2g, 2g + 1, 8 + 2g, 9 + 2g
   const int64_t N = a.n_rays * (int64_t)a.S;  // a multiple of 64
-  // software-pipelined two tile pairs deep: the loads of the next two pairs (enc, dsigma) are in flight
-  // while this one computes (2 waves per SIMD at this register count: latency is hidden by ILP)
-  const int64_t step = (int64_t)gridDim.x * kWavesPerBlock * 32;
-  int64_t n0 = ((int64_t)blockIdx.x * kWavesPerBlock + wid) * 32;
   struct Pre {
     uint32_t x0[4], x1[4];
     float d0, d1;
@@ -1255,113 +1198,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MLP
     p.d0 = ld_off(a.d_sigma, mb);
     p.d1 = ld_off(a.d_sigma, mb + 64u);
   };
-  auto pair = [&](int64_t n0, const Pre& p) {
-    SigmaHidden h0, h1;
-    half8_t e0, e1;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      e0[2 * q + 0] = __builtin_bit_cast(_Float16, (uint16_t)(p.x0[q] & 0xFFFFu));
-      e0[2 * q + 1] = __builtin_bit_cast(_Float16, (uint16_t)(p.x0[q] >> 16));
-      e1[2 * q + 0] = __builtin_bit_cast(_Float16, (uint16_t)(p.x1[q] & 0xFFFFu));
-      e1[2 * q + 1] = __builtin_bit_cast(_Float16, (uint16_t)(p.x1[q] >> 16));
-    }
-    const float ds0 = p.d0, ds1 = p.d1;
-    (void)sigma_tile_fwd(sw, e0, h0);
-    (void)sigma_tile_fwd(sw, e1, h1);
-    float mx = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      dw1[k] = fmaf(ds0, h0[k], dw1[k]);
-      dw1[k] = fmaf(ds1, h1[k], dw1[k]);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fmaxf(fabsf((float)e0[j] * ds0), fabsf((float)e1[j] * ds1)));
-    const float pair_max = wave_max(mx);
-    float d[2][4];
-    sigma_tile_bwd_denc(sw, h0, d);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int lvl = 8 * m + 2 * g;
-      const float2 q0 = make_float2(d[m][0] * ds0, d[m][1] * ds0), q1 = make_float2(d[m][2] * ds0, d[m][3] * ds0);
-      if (JAC) {
-        const uint32_t o = row_j + 8u * (uint32_t)m * st4 + (uint32_t)(n0 + c) * 4u;
-        st_off(a.d_jac, o, pack_h2(d[m][0], d[m][1]));
-        st_off(a.d_jac, o + st4, pack_h2(d[m][2], d[m][3]));
-      } else {
-        denc[(int64_t)lvl * a.enc_stride + n0 + c] = q0;
-        denc[(int64_t)(lvl + 1) * a.enc_stride + n0 + c] = q1;
-      }
-      lmax[2 * m] = fmaxf(lmax[2 * m], fmaxf(fabsf(q0.x), fabsf(q0.y)));
-      lmax[2 * m + 1] = fmaxf(lmax[2 * m + 1], fmaxf(fabsf(q1.x), fabsf(q1.y)));
-    }
-    sigma_tile_bwd_denc(sw, h1, d);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int lvl = 8 * m + 2 * g;
-      const float2 q0 = make_float2(d[m][0] * ds1, d[m][1] * ds1), q1 = make_float2(d[m][2] * ds1, d[m][3] * ds1);
-      if (JAC) {
-        const uint32_t o = row_j + 8u * (uint32_t)m * st4 + (uint32_t)(n0 + 16 + c) * 4u;
-        st_off(a.d_jac, o, pack_h2(d[m][0], d[m][1]));
-        st_off(a.d_jac, o + st4, pack_h2(d[m][2], d[m][3]));
-      } else {
-        denc[(int64_t)lvl * a.enc_stride + n0 + 16 + c] = q0;
-        denc[(int64_t)(lvl + 1) * a.enc_stride + n0 + 16 + c] = q1;
-      }
-      lmax[2 * m] = fmaxf(lmax[2 * m], fmaxf(fabsf(q0.x), fabsf(q0.y)));
-      lmax[2 * m + 1] = fmaxf(lmax[2 * m + 1], fmaxf(fabsf(q1.x), fabsf(q1.y)));
-    }
-    dw0_pair_mfma(lds, h0, h1, e0, e1, ds0, ds1, pair_max, acc);
-  };
-  // the same pair with one tile live at a time: the pair's operand scale first (from the inputs), then
-  // per tile the forward, dW1, its dW0 operands staged in LDS, its d_enc; the dW0 MFMAs last
-  auto pair_split = [&](int64_t n0, const Pre& p) {
-    float mx = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float a0 = (float)__builtin_bit_cast(_Float16, (uint16_t)(p.x0[q] & 0xFFFFu));
-      const float b0 = (float)__builtin_bit_cast(_Float16, (uint16_t)(p.x0[q] >> 16));
-      const float a1 = (float)__builtin_bit_cast(_Float16, (uint16_t)(p.x1[q] & 0xFFFFu));
-      const float b1 = (float)__builtin_bit_cast(_Float16, (uint16_t)(p.x1[q] >> 16));
-      mx = fmaxf(mx, fmaxf(fabsf(a0 * p.d0), fabsf(a1 * p.d1)));
-      mx = fmaxf(mx, fmaxf(fabsf(b0 * p.d0), fabsf(b1 * p.d1)));
-    }
-    float scale = 1.f;
-    const bool dw0 = dw0_scale(wave_max(mx), acc, scale);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      half8_t e;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint32_t x = t ? p.x1[q] : p.x0[q];
-        e[2 * q + 0] = __builtin_bit_cast(_Float16, (uint16_t)(x & 0xFFFFu));
-        e[2 * q + 1] = __builtin_bit_cast(_Float16, (uint16_t)(x >> 16));
-      }
-      const float ds = t ? p.d1 : p.d0;
-      SigmaHidden h;
-      (void)sigma_tile_fwd(sw, e, h);
-#pragma unroll
-      for (int k = 0; k < 16; ++k) dw1[k] = fmaf(ds, h[k], dw1[k]);
-      if (dw0) dw0_stage(lds, t, h, e, ds * scale);
-      float d[2][4];
-      sigma_tile_bwd_denc(sw, h, d);
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const int lvl = 8 * m + 2 * g;
-        const float2 q0 = make_float2(d[m][0] * ds, d[m][1] * ds), q1 = make_float2(d[m][2] * ds, d[m][3] * ds);
-        if (JAC) {
-          const uint32_t o = row_j + 8u * (uint32_t)m * st4 + (uint32_t)(n0 + 16 * t + c) * 4u;
-          st_off(a.d_jac, o, pack_h2(d[m][0], d[m][1]));
-          st_off(a.d_jac, o + st4, pack_h2(d[m][2], d[m][3]));
-        } else {
-          denc[(int64_t)lvl * a.enc_stride + n0 + 16 * t + c] = q0;
-          denc[(int64_t)(lvl + 1) * a.enc_stride + n0 + 16 * t + c] = q1;
-        }
-        lmax[2 * m] = fmaxf(lmax[2 * m], fmaxf(fabsf(q0.x), fabsf(q0.y)));
-        lmax[2 * m + 1] = fmaxf(lmax[2 * m + 1], fmaxf(fabsf(q1.x), fabsf(q1.y)));
-      }
-    }
-    if (dw0) dw0_mfma(lds, acc);
-  };
   auto pair_pk = [&](int64_t n0, const Pre& p) {
     uint32_t hw[2][8];
     sigma_tile_fwd_pk(sw, p.x0, hw[0]);
@@ -1375,7 +1211,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MLP
       dw1[k] = fmaf(ds[1], h1, dw1[k]);
     }
     // max |e ds| over the pair: |ds| max |e| (rounding is monotonic: the same value)
-    // (on DPP, wave-uniform; the same value as dw0_pair_mfma's wave_max for finite inputs)
+    // (on DPP, wave-uniform; the same value as wave_max of the per-value products for finite inputs)
     const float pair_max = wave_max_nonneg(fmaxf(enc_absmax(p.x0) * fabsf(ds[0]), enc_absmax(p.x1) * fabsf(ds[1])));
     const uint32_t* w1w = reinterpret_cast<const uint32_t*>(&sw.w1h[0]);
     uint32_t mk[2][8];
@@ -1412,20 +1248,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MLP
         }
       }
     }
-#ifdef LNR_MLP_PK_OLDDW0
-    {
-      SigmaHidden H[2];
-      half8_t E[2];
-      for (int t = 0; t < 2; ++t) {
-        H[t].q[0] = __builtin_bit_cast(half8_t, (u32x4){hw[t][0], hw[t][1], hw[t][2], hw[t][3]});
-        H[t].q[1] = __builtin_bit_cast(half8_t, (u32x4){hw[t][4], hw[t][5], hw[t][6], hw[t][7]});
-        const uint32_t* x = t ? p.x1 : p.x0;
-        E[t] = __builtin_bit_cast(half8_t, (u32x4){x[0], x[1], x[2], x[3]});
-      }
-      dw0_pair_mfma(lds, H[0], H[1], E[0], E[1], ds[0], ds[1], pair_max, acc);
-      return;
-    }
-#endif
     float scale = 1.f;
     if (!dw0_scale(pair_max, acc, scale)) return;  // (wave-uniform) the pair adds nothing to dW0
     uint32_t* img = reinterpret_cast<uint32_t*>(lds);
@@ -1438,8 +1260,9 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MLP
             (u32x2){mk[t][2 * tt] & 0x3C003C00u, mk[t][2 * tt + 1] & 0x3C003C00u};
       const float st = ds[t] * scale;
       const uint32_t* x = t ? p.x1 : p.x0;
-      // (fp32 product, then rounded to fp16, as written: dw0_pair_mfma's same expression compiles to v_fma_mixlo,
-      // one rounding of the exact product, so a rare tie rounds differently there: tools/mlp_bwd_dump.py)
+      // (fp32 product, then rounded to fp16, as written: v_pk_mul_f32, then v_cvt_pk_f16_f32.  The same
+      // expression on one value at a time compiles to v_fma_mixlo, one rounding of the exact product, and a rare tie
+      // rounds differently there: DESIGN.md retired variants, tools/mlp_bwd_dump.py)
       const half8_t e = __builtin_bit_cast(half8_t, (u32x4){x[0], x[1], x[2], x[3]});
       half8_t es;
 #pragma unroll
@@ -1468,30 +1291,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MLP
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
   };
-#if LNR_MLP_PK
-#define LNR_MLP_PAIR pair_pk
-#elif LNR_MLP_SPLIT_PAIR
-#define LNR_MLP_PAIR pair_split
-#else
-#define LNR_MLP_PAIR pair
-#endif
-#if LNR_MLP_PREFETCH == 2
-  Pre pa, pb;
-  prefetch(n0, pa);
-  prefetch(n0 + step, pb);
-  for (; n0 < N; n0 += 2 * step) {
-    {
-      const Pre cur = pa;
-      prefetch(n0 + 2 * step, pa);
-      LNR_MLP_PAIR(n0, cur);
-    }
-    if (n0 + step < N) {  // (wave-uniform)
-      const Pre cur = pb;
-      prefetch(n0 + 3 * step, pb);
-      LNR_MLP_PAIR(n0 + step, cur);
-    }
-  }
-#else
   // A pair whose 32 d sigma are all 0 (relu(sigma + noise) = 0 for every sample: most pairs of a trained field's
   // free space) adds exact zeros to dW1 and to the level maxima and nothing to dW0 (dw0_scale refuses a zero
   // pair_max), and its d_enc is 0: it is skipped, its encodings not even loaded and its J not written (consumers
@@ -1536,10 +1335,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(LNR_MLP
     const int64_t m = nm;
     nm = next_live();
     if (nm >= 0) prefetch(nm, pa);
-    LNR_MLP_PAIR(m, cur);
+    pair_pk(m, cur);
   }
-#endif
-#undef LNR_MLP_PAIR
   __syncthreads();
   {
     DW0Acc out;
@@ -1585,8 +1382,7 @@ __global__ void __launch_bounds__(256) k_denc_max(const float2* __restrict__ d_e
 
 static size_t wave_smem_bytes(int S) { return (size_t)kWavesPerBlock * S * 4; }
 static size_t bwd_tiles_smem_bytes() {
-  // per-wave dW0 staging, then (LNR_MLP_W_LDS) the 8 weight operands x 64 lanes x 16 B
-  const size_t b = (size_t)kWavesPerBlock * (64 * 32 + 32 * 32) * 2 + (LNR_MLP_W_LDS ? 8 * 64 * 16 : 0);
+  const size_t b = (size_t)kWavesPerBlock * (64 * 32 + 32 * 32) * 2;  // per-wave dW0 staging
   return b < LNR_SIGMA_MLP_PARAMS * 4 ? LNR_SIGMA_MLP_PARAMS * 4 : b;
 }
 
@@ -1677,6 +1473,22 @@ static int launch_field(const FieldArgs& a, int nblocks, hipStream_t st, const c
 
 static int field_blocks(int64_t n_rays) { return (int)(n_rays < 1024 ? n_rays : 1024); }
 
+// The fields every entry point fills alike: the rays, their samples and the compositing's noise
+static FieldArgs field_args(const float* rays, const float* z, int64_t n_rays, int32_t S, float noise_std,
+                            const float* noise, uint32_t key, int64_t ray_offset) {
+  FieldArgs a{};
+  a.rays = rays; a.z = z; a.n_rays = n_rays; a.S = S;
+  a.noise_std = noise_std; a.noise = noise; a.key = key; a.ray_offset = ray_offset;
+  return a;
+}
+
+// k_sigma_fwd_tiles over every 64-sample unit of the batch: sigma into a.d_sigma
+static void launch_sigma_fwd_tiles(const FieldArgs& a, hipStream_t st) {
+  const int64_t units = a.n_rays * (int64_t)a.S / kSigmaFwdUnit;
+  const int64_t wantu = (units + kWavesPerBlock - 1) / kWavesPerBlock;
+  hipLaunchKernelGGL(k_sigma_fwd_tiles, dim3((int)(wantu < 8192 ? wantu : 8192)), dim3(NT), 0, st, a);
+}
+
 }  // namespace lnr
 
 using namespace lnr;
@@ -1707,9 +1519,8 @@ extern "C" int lnr_composite(const float* rays, const float* z, const float* sig
               "Unknown render strategy: %d", strategy);  // rendering_tcnn.py:403-404 raises ValueError
   if (n_rays == 0) return LNR_OK;
   LNR_REQUIRE(sigma && depth, "lnr_composite: null sigma/depth");
-  FieldArgs a{};
-  a.rays = rays; a.z = z; a.sigma_in = sigma; a.n_rays = n_rays; a.S = n_samples;
-  a.noise_std = noise_std; a.noise = noise; a.key = key; a.ray_offset = ray_offset;
+  FieldArgs a = field_args(rays, z, n_rays, n_samples, noise_std, noise, key, ray_offset);
+  a.sigma_in = sigma;
   a.weights = weights; a.depth = depth; a.opacity = opacity; a.variance = variance;
   const int nb = field_blocks(n_rays);
   if (strategy == LNR_RENDER_ADJUSTED)
@@ -1731,9 +1542,8 @@ extern "C" int lnr_composite_loss_bwd(const float* rays, const float* z, const f
   if (int e = check_lp(lp, "lnr_composite_loss_bwd")) return e;
   if (n_rays == 0) return LNR_OK;
   LNR_REQUIRE(sigma && depth_gt && d_sigma && ray_stats, "lnr_composite_loss_bwd: null pointer");
-  FieldArgs a{};
-  a.rays = rays; a.z = z; a.sigma_in = sigma; a.depth_gt = depth_gt; a.n_rays = n_rays; a.S = n_samples;
-  a.noise_std = noise_std; a.noise = noise; a.key = key; a.ray_offset = ray_offset; a.lp = *lp;
+  FieldArgs a = field_args(rays, z, n_rays, n_samples, noise_std, noise, key, ray_offset);
+  a.sigma_in = sigma; a.depth_gt = depth_gt; a.lp = *lp;
   a.weights = weights; a.depth = depth; a.opacity = opacity; a.d_sigma = d_sigma; a.ray_stats = ray_stats;
   return launch_field<true, false, kSigmaGiven>(a, field_blocks(n_rays), as_stream(stream), "lnr_composite_loss_bwd");
 }
@@ -1748,9 +1558,8 @@ extern "C" int lnr_composite_bwd(const float* rays, const float* z, const float*
               "Unknown render strategy: %d", strategy);
   if (n_rays == 0) return LNR_OK;
   LNR_REQUIRE(sigma && d_sigma, "lnr_composite_bwd: null sigma/d_sigma");
-  FieldArgs a{};
-  a.rays = rays; a.z = z; a.sigma_in = sigma; a.n_rays = n_rays; a.S = n_samples;
-  a.noise_std = noise_std; a.noise = noise; a.key = key; a.ray_offset = ray_offset;
+  FieldArgs a = field_args(rays, z, n_rays, n_samples, noise_std, noise, key, ray_offset);
+  a.sigma_in = sigma;
   a.lp.kind = kLossExternal;
   a.g_weights = g_weights; a.g_depth = g_depth; a.g_opacity = g_opacity; a.g_variance = g_variance;
   a.d_sigma = d_sigma;
@@ -1792,10 +1601,9 @@ extern "C" int lnr_field_train(const uint16_t* w, const uint32_t* enc, int64_t e
               "lnr_field_train: d_enc_jac needs n_samples in {64, 128, 256, 512} (got %d)", n_samples);
   LNR_REQUIRE(enc_stride < (int64_t(1) << 26), "lnr_field_train: enc_stride=%lld over 2^26 (32-bit level offsets)",
               (long long)enc_stride);
-  FieldArgs a{};
-  a.w = w; a.enc = enc; a.enc_stride = enc_stride; a.rays = rays; a.z = z; a.depth_gt = depth_gt;
-  a.n_rays = n_rays; a.S = n_samples; a.noise_std = noise_std; a.noise = noise; a.key = key;
-  a.ray_offset = ray_offset; a.lp = *lp; a.d_enc = d_enc; a.dw_slab = workspace; a.ray_stats = ray_stats;
+  FieldArgs a = field_args(rays, z, n_rays, n_samples, noise_std, noise, key, ray_offset);
+  a.w = w; a.enc = enc; a.enc_stride = enc_stride; a.depth_gt = depth_gt;
+  a.lp = *lp; a.d_enc = d_enc; a.dw_slab = workspace; a.ray_stats = ray_stats;
   a.depth = depth; a.opacity = opacity; a.weights = weights; a.denc_max = d_enc_level_max; a.d_jac = d_enc_jac;
   a.d_ray = lp->dev_d_ray;
   hipStream_t st = as_stream(stream);
@@ -1811,29 +1619,17 @@ extern "C" int lnr_field_train(const uint16_t* w, const uint32_t* enc, int64_t e
     const int64_t want = (n_rays + kWavesPerBlock - 1) / kWavesPerBlock;
     const int nr = (int)(want < 2048 ? want : 2048);
     const size_t sm = wave_smem_bytes(n_samples);
-#if LNR_FIELD_SPLIT
     if (!bwd_only) {
-    if (!(lp->flags & LNR_LP_SIGMA_READY)) {  // (early ray termination: lnr_field_sigma_phase wrote sigma)
-      const int64_t units = n_rays * (int64_t)n_samples / kSigmaFwdUnit;
-      const int64_t wantu = (units + kWavesPerBlock - 1) / kWavesPerBlock;
-      hipLaunchKernelGGL(k_sigma_fwd_tiles, dim3((int)(wantu < 8192 ? wantu : 8192)), dim3(NT), 0, st, a);
-    }
-    switch (C) {
-      case 1: hipLaunchKernelGGL(k_composite_wave<1>, dim3(nr), dim3(NT), sm, st, a); break;
-      case 2: hipLaunchKernelGGL(k_composite_wave<2>, dim3(nr), dim3(NT), sm, st, a); break;
-      case 4: hipLaunchKernelGGL(k_composite_wave<4>, dim3(nr), dim3(NT), sm, st, a); break;
-      default: hipLaunchKernelGGL(k_composite_wave<8>, dim3(nr), dim3(NT), sm, st, a); break;
-    }
+      // (early ray termination: lnr_field_sigma_phase wrote sigma)
+      if (!(lp->flags & LNR_LP_SIGMA_READY)) launch_sigma_fwd_tiles(a, st);
+      switch (C) {
+        case 1: hipLaunchKernelGGL(k_composite_wave<1>, dim3(nr), dim3(NT), sm, st, a); break;
+        case 2: hipLaunchKernelGGL(k_composite_wave<2>, dim3(nr), dim3(NT), sm, st, a); break;
+        case 4: hipLaunchKernelGGL(k_composite_wave<4>, dim3(nr), dim3(NT), sm, st, a); break;
+        default: hipLaunchKernelGGL(k_composite_wave<8>, dim3(nr), dim3(NT), sm, st, a); break;
+      }
     }
     if (fwd_only) LNR_RETURN_LAUNCH("lnr_field_train(forward)");
-#else
-    switch (C) {
-      case 1: hipLaunchKernelGGL(k_field_wave<1>, dim3(nr), dim3(NT), sm, st, a); break;
-      case 2: hipLaunchKernelGGL(k_field_wave<2>, dim3(nr), dim3(NT), sm, st, a); break;
-      case 4: hipLaunchKernelGGL(k_field_wave<4>, dim3(nr), dim3(NT), sm, st, a); break;
-      default: hipLaunchKernelGGL(k_field_wave<8>, dim3(nr), dim3(NT), sm, st, a); break;
-    }
-#endif
     const int64_t pairs = (n_rays * (int64_t)n_samples) / 32;
     const int64_t wantb = (pairs + kWavesPerBlock - 1) / kWavesPerBlock;
     const int64_t slabs = lnr_dw_workspace_words(n_rays) / LNR_SIGMA_MLP_PARAMS;  // one dW slab per block
@@ -1877,9 +1673,8 @@ extern "C" int lnr_field_sigma_phase(const uint16_t* w, const uint32_t* enc, int
               "lnr_field_sigma_phase: null pointer (a phase after the first needs the list of rays still alive)");
   LNR_REQUIRE(hi == n_samples || (list_out && count_out && transmittance && scratch),
               "lnr_field_sigma_phase: null pointer (the phase's transmittance update)");
-  FieldArgs a{};
-  a.w = w; a.enc = enc; a.enc_stride = enc_stride; a.rays = rays; a.z = z; a.n_rays = n_rays; a.S = n_samples;
-  a.noise_std = noise_std; a.noise = noise; a.key = key; a.ray_offset = ray_offset;
+  FieldArgs a = field_args(rays, z, n_rays, n_samples, noise_std, noise, key, ray_offset);
+  a.w = w; a.enc = enc; a.enc_stride = enc_stride;
   if (lp) a.lp = *lp;
   a.d_sigma = workspace + lnr_dw_workspace_words(n_rays);
   hipStream_t st = as_stream(stream);
@@ -1912,9 +1707,8 @@ extern "C" int lnr_field_ert_march(const lnr_grid_desc* d, const uint16_t* table
   if (n_rays == 0) return LNR_OK;
   LNR_REQUIRE(table && enc && w && workspace && list_in && count_in && transmittance,
               "lnr_field_ert_march: null pointer");
-  FieldArgs a{};
-  a.w = w; a.enc = enc; a.enc_stride = enc_stride; a.rays = rays; a.z = z; a.n_rays = n_rays; a.S = n_samples;
-  a.noise_std = noise_std; a.noise = noise; a.key = key; a.ray_offset = ray_offset;
+  FieldArgs a = field_args(rays, z, n_rays, n_samples, noise_std, noise, key, ray_offset);
+  a.w = w; a.enc = enc; a.enc_stride = enc_stride;
   if (lp) a.lp = *lp;
   a.d_sigma = workspace + lnr_dw_workspace_words(n_rays);
   const GridArgs ga = make_args(d, n_samples);
@@ -1936,26 +1730,21 @@ extern "C" int lnr_field_render(const uint16_t* w, const uint32_t* enc, int64_t 
   LNR_REQUIRE(enc_stride >= n_rays * (int64_t)n_samples, "lnr_field_render: enc_stride too small");
   if (n_rays == 0) return LNR_OK;
   LNR_REQUIRE(w && enc && depth, "lnr_field_render: null pointer");
-  FieldArgs a{};
-  a.w = w; a.enc = enc; a.enc_stride = enc_stride; a.rays = rays; a.z = z; a.n_rays = n_rays; a.S = n_samples;
-  a.noise_std = noise_std; a.noise = noise; a.key = key; a.ray_offset = ray_offset;
+  FieldArgs a = field_args(rays, z, n_rays, n_samples, noise_std, noise, key, ray_offset);
+  a.w = w; a.enc = enc; a.enc_stride = enc_stride;
   a.depth = depth; a.opacity = opacity; a.variance = variance; a.weights = weights;
   const int nb = field_blocks(n_rays);
-#if LNR_FIELD_SPLIT
   if (weights) {
     // the sigma MLP tile-parallel first (k_sigma_fwd_tiles), its sigma staged in the weights buffer,
     // which the compositing reads into LDS one ray at a time before it writes that ray's weights
     hipStream_t st = as_stream(stream);
     a.d_sigma = weights;
-    const int64_t units = n_rays * (int64_t)n_samples / kSigmaFwdUnit;
-    const int64_t wantu = (units + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL(k_sigma_fwd_tiles, dim3((int)(wantu < 8192 ? wantu : 8192)), dim3(NT), 0, st, a);
+    launch_sigma_fwd_tiles(a, st);
     a.d_sigma = nullptr;
     a.sigma_in = weights;
     if (strategy == LNR_RENDER_ADJUSTED) return launch_field<false, true, kSigmaGiven>(a, nb, st, "lnr_field_render");
     return launch_field<false, false, kSigmaGiven>(a, nb, st, "lnr_field_render");
   }
-#endif
   if (strategy == LNR_RENDER_ADJUSTED)
     return launch_field<false, true, kSigmaMLP>(a, nb, as_stream(stream), "lnr_field_render");
   return launch_field<false, false, kSigmaMLP>(a, nb, as_stream(stream), "lnr_field_render");

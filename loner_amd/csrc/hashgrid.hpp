@@ -507,9 +507,6 @@ __device__ __forceinline__ RunInfo cell_runs_dpp(bool in, uint32_t cx, uint32_t 
         "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]),        \
         "+v"(v[15])                                                                                      \
       : "v"(f))
-#ifndef LNR_SEG_FMAC
-#define LNR_SEG_FMAC 1  // the segmented sums as v_fmac_f32_dpp (1) or DPP move + masked add (0)
-#endif
 
 // Segmented inclusive sum of N values over runs sharing one RunInfo: the run's tail lane ends with
 // the run totals.  Each step's lane condition is computed once for all N values.  Fixed order:
@@ -522,7 +519,7 @@ __device__ __forceinline__ void run_sum_dpp_n(const RunInfo& ri, float (&v)[N]) 
   const int lane = threadIdx.x & 63;
   const int h = ri.head_lane;
   const int rs = lane & ~15;
-  if constexpr (LNR_SEG_FMAC && N == 16) {
+  if constexpr (N == 16) {
     // (branching around a step would cost the register copies the compiler places at the joins; a
     // step no run needs multiplies by 0 everywhere)
     LNR_FMAC_DPP_16("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1", v, (lane - 1 >= h) ? 1.f : 0.f);

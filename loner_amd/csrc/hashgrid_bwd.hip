@@ -361,9 +361,7 @@ constexpr int kCap = 4 * kSB + 256;
 // and r+1 write adjacent runs in every bucket: their boundary lines are completed in one XCD's L2
 // only if both rows run there.  So XCD x takes the contiguous rows [x n/8, (x+1) n/8), in order.
 __device__ __forceinline__ int64_t xcd_row(uint32_t bx, uint32_t n) {
-#ifndef LNR_EXP_NO_XCD_ROWS
   if ((n & 7u) == 0) return (int64_t)(bx & 7u) * (n >> 3) + (bx >> 3);
-#endif
   return bx;
 }  // 4 records per sample at fine levels, plus slack
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -590,12 +588,9 @@ constexpr int kRowsCap = 2176;  // 4.25 records per sample: fine rows hold 4 + t
 // per CU (C2: 670 against 627 us).  GradF32's float2 gradients need 16 more registers: they keep
 // the double-buffered stage at 4 waves per SIMD (one stage would spill), except with 128 chunks
 // per level (the colour grid), whose tables leave room for one stage only.
-#ifndef LNR_SCATTER_STAGES
-#define LNR_SCATTER_STAGES 0  // 0: per gradient source as above; 1 or 2: forced (experiments)
-#endif
 template <class GradFn, int NB>
 constexpr int rows_stages() {
-  return LNR_SCATTER_STAGES ? LNR_SCATTER_STAGES : (sizeof(typename GradFn::Raw) <= 4 || NB > 64 ? 1 : 2);
+  return sizeof(typename GradFn::Raw) <= 4 || NB > 64 ? 1 : 2;
 }
 #ifndef LNR_ROWS_WIDE_WAVES
 // One stage with float2 gradients (GradF32: the colour grid's backward): 6 waves cap it at 80 VGPRs
@@ -606,28 +601,16 @@ template <class GradFn, int NB>
 constexpr int rows_waves() {
   return rows_stages<GradFn, NB>() == 2 ? 4 : (sizeof(typename GradFn::Raw) > 4 ? LNR_ROWS_WIDE_WAVES : 6);
 }
-#ifndef LNR_PRESCALE
-#define LNR_PRESCALE 1
-#endif
-#ifndef LNR_ROWS_NB128
-#define LNR_ROWS_NB128 1  // the level-looped scatter for grids with up to 128 chunks per level too
-#endif
-#ifndef LNR_ROWS_SOA
-#define LNR_ROWS_SOA 1
-#endif
 template <int NL, int NB, int STG>
 struct RowsLds {  // the small tables first: their addresses fit the 16-bit LDS instruction offset
   uint2 sg[NL][NB];           // per level and bucket: {start in the stage, global slot of the run}
   uint32_t total[NL];         // records of the row at each level
   uint32_t ctr[2][NB];        // rank counters
   LevelParams lv[NL];         // the level table (kernel arguments indexed per level would be loads)
-#if LNR_ROWS_SOA
-  // staged records in bucket order, one array per field: a record's three stores go to bank slot mod 32 each
-  // (with 16-byte records a store's 32 lanes, at random slots, met only 8 banks: 4 slot mod 8 + field)
+  // staged records {word, global slot, fp16 value pair} in bucket order, one array per field: a record's three
+  // stores go to bank slot mod 32 each (with 16-byte records a store's 32 lanes, at random slots, met only 8
+  // banks: 4 slot mod 8 + field)
   uint32_t st_word[STG][kRowsCap], st_slot[STG][kRowsCap], st_val[STG][kRowsCap];
-#else
-  uint4 stage[STG][kRowsCap];  // staged records {word, global slot, fp16 value pair, -}, bucket order
-#endif
 };
 
 // NL levels, the first NM coherent (run-merging) and the rest fine, at most NB buckets per level:
@@ -717,26 +700,13 @@ __device__ __forceinline__ void scatter_rows_body(RowsLds<NL, NB, kRowsStages>& 
 
   // staged record t of stage b as {word, global slot, fp16 pair, -}
   auto staged_rec = [&](int b, uint32_t t) {
-#if LNR_ROWS_SOA
     return make_uint4(sm.st_word[b][t], sm.st_slot[b][t], sm.st_val[b][t], 0u);
-#else
-    return sm.stage[b][t];
-#endif
   };
   // copy level l's staged row out (consecutive threads -> consecutive slots of a run)
   auto copy_out = [&](uint32_t l) {
     const int sbuf = kRowsStages == 2 ? (l & 1) : 0;
     const uint32_t total = sm.total[l];
     const uint32_t lim = total <= (uint32_t)kRowsCap ? total : 0u;
-#if LNR_COPY_ALL_TRIPS
-#pragma unroll
-    for (int u = 0; u < (kRowsCap + kSB - 1) / kSB; ++u) {
-      const uint32_t t = threadIdx.x + u * kSB;
-      const uint4 q = staged_rec(sbuf, t < (uint32_t)kRowsCap ? t : kRowsCap - 1);
-      const uint32_t d = t < lim && q.y < spare ? q.y : spare;  // (the bound: never a store outside the records)
-      ws.rec[d] = make_uint2(q.x, q.z);
-    }
-#else
     // only the trips the row's records need (block-uniform: a merged coherent row holds far fewer
     // than kRowsCap), and only the lanes holding a record store
 #pragma unroll
@@ -750,7 +720,6 @@ __device__ __forceinline__ void scatter_rows_body(RowsLds<NL, NB, kRowsStages>& 
         }
       }
     }
-#endif
   };
 
 #pragma unroll
@@ -762,15 +731,11 @@ __device__ __forceinline__ void scatter_rows_body(RowsLds<NL, NB, kRowsStages>& 
     uint32_t* ctr = sm.ctr[sbuf];
     const uint2* sgl = sm.sg[l];
     const float2 gl = GradFn::finish(g[l], gsc);
-#if LNR_PRESCALE
     // the level's record scale applied to the gradient once, not to every record value: a power of
     // two, so w (g 2^k) rounds exactly as (w g) 2^k
     const float2 gv = in ? make_float2(gl.x * rsc[l], gl.y * rsc[l]) : make_float2(0.f, 0.f);
-#else
-    const float2 gv = in ? gl : make_float2(0.f, 0.f);
-#endif
     const bool act = LIVE ? lv_live : in && live && (!skip_zero || gv.x != 0.f || gv.y != 0.f);
-    const float rs = LNR_PRESCALE ? 1.0f : rsc[l];
+    const float rs = 1.0f;  // (the values are scaled already)
     // rank (returning LDS atomics) and place: all start reads, then all atomics, then all writes
     // (one lane-level branch for the 4 records: they share their validity)
     auto place = [&](bool valid, const uint32_t (&bk)[4], const uint32_t (&word)[4], const float2 (&val)[4]) {
@@ -786,18 +751,10 @@ __device__ __forceinline__ void scatter_rows_body(RowsLds<NL, NB, kRowsStages>& 
           const uint32_t slot = s4[k].y + rank[k];
           const uint32_t h = rec_half2(val[k].x, val[k].y, rs);
           if (staged) {
-#if LNR_ROWS_SOA
             const uint32_t t = s4[k].x + rank[k];
             sm.st_word[stg][t] = word[k];
             sm.st_slot[stg][t] = slot;
             sm.st_val[stg][t] = h;
-#else
-            // three 32-bit fields (ds_write2_b32 + ds_write_b32: no register moves for a b128 quad)
-            uint32_t* q = reinterpret_cast<uint32_t*>(&sm.stage[stg][s4[k].x + rank[k]]);
-            q[0] = word[k];
-            q[1] = slot;
-            q[2] = h;
-#endif
           } else {  // (block-uniform) more records than the stage holds: each straight to its global slot
             ws.rec[slot < spare ? slot : spare] = make_uint2(word[k], h);
           }
@@ -1578,31 +1535,33 @@ static int launch_bwd_bucketed(const lnr_grid_desc* d, PosFn pos, int64_t n, Gra
   if (prepared) {
     w.use_live = live;  // (the prepare call's scans cover the live rows)
   } else {
-  if (!(flags & LNR_BWD_COUNTS_READY) && !live)
-    hipLaunchKernelGGL((k_bwd_count<PosFn, GradFn>), dim3((unsigned)w.n_sb, d->n_levels), dim3(kSB), 0, st, a, pos, n,
-                       grad, w);
-  if (w.n_chunks > 1 && !live)
-    hipLaunchKernelGGL(k_bwd_chunk_sums, dim3((unsigned)w.n_chunks, d->n_levels), dim3(kMaxChunksPerLevel), 0, st, a, w);
-  if (live) {
-    if constexpr (GradFn::kScaled) {
-      const int64_t n_waves = (n + 63) / 64;
-      hipLaunchKernelGGL(k_bwd_live_flags, dim3((unsigned)((n_waves * 16 + 255) / 256)), dim3(256), 0, st, grad.dsig, n, w);
-      hipLaunchKernelGGL(k_bwd_live_list, dim3(1), dim3(1024), 0, st, n_waves, w);
-      auto cnt = m == 3   ? k_bwd_count_live<PosFn, 16, 3, 64>
-                 : m == 4 ? k_bwd_count_live<PosFn, 16, 4, 64>
-                 : m == 5 ? k_bwd_count_live<PosFn, 16, 5, 64>
-                 : m == 6 ? k_bwd_count_live<PosFn, 16, 6, 64>
-                          : k_bwd_count_live<PosFn, 16, 7, 64>;
-      hipLaunchKernelGGL(cnt, dim3((unsigned)w.n_sb), dim3(kSB), 0, st, a, pos, n, grad.dsig, w);
-      w.use_live = true;  // the scans and the scatter below: the live rows
-      if (w.n_chunks > 1)
-        hipLaunchKernelGGL(k_bwd_chunk_sums, dim3((unsigned)w.n_chunks, d->n_levels), dim3(kMaxChunksPerLevel), 0, st, a,
+    if (!(flags & LNR_BWD_COUNTS_READY) && !live)
+      hipLaunchKernelGGL((k_bwd_count<PosFn, GradFn>), dim3((unsigned)w.n_sb, d->n_levels), dim3(kSB), 0, st, a, pos, n,
+                         grad, w);
+    if (w.n_chunks > 1 && !live)
+      hipLaunchKernelGGL(k_bwd_chunk_sums, dim3((unsigned)w.n_chunks, d->n_levels), dim3(kMaxChunksPerLevel), 0, st, a,
+                         w);
+    if (live) {
+      if constexpr (GradFn::kScaled) {
+        const int64_t n_waves = (n + 63) / 64;
+        hipLaunchKernelGGL(k_bwd_live_flags, dim3((unsigned)((n_waves * 16 + 255) / 256)), dim3(256), 0, st, grad.dsig, n,
                            w);
+        hipLaunchKernelGGL(k_bwd_live_list, dim3(1), dim3(1024), 0, st, n_waves, w);
+        auto cnt = m == 3   ? k_bwd_count_live<PosFn, 16, 3, 64>
+                   : m == 4 ? k_bwd_count_live<PosFn, 16, 4, 64>
+                   : m == 5 ? k_bwd_count_live<PosFn, 16, 5, 64>
+                   : m == 6 ? k_bwd_count_live<PosFn, 16, 6, 64>
+                            : k_bwd_count_live<PosFn, 16, 7, 64>;
+        hipLaunchKernelGGL(cnt, dim3((unsigned)w.n_sb), dim3(kSB), 0, st, a, pos, n, grad.dsig, w);
+        w.use_live = true;  // the scans and the scatter below: the live rows
+        if (w.n_chunks > 1)
+          hipLaunchKernelGGL(k_bwd_chunk_sums, dim3((unsigned)w.n_chunks, d->n_levels), dim3(kMaxChunksPerLevel), 0, st, a,
+                             w);
+      }
     }
-  }
-  hipLaunchKernelGGL(k_bwd_scan_rows, dim3((unsigned)w.n_chunks, d->n_levels), dim3(kMaxChunksPerLevel), 0, st, a, w);
-  hipLaunchKernelGGL(k_bwd_scan_buckets, dim3(1), dim3(1024), 0, st, w, a.n_buckets);
-  if (prepare_only) LNR_RETURN_LAUNCH(who);
+    hipLaunchKernelGGL(k_bwd_scan_rows, dim3((unsigned)w.n_chunks, d->n_levels), dim3(kMaxChunksPerLevel), 0, st, a, w);
+    hipLaunchKernelGGL(k_bwd_scan_buckets, dim3(1), dim3(1024), 0, st, w, a.n_buckets);
+    if (prepare_only) LNR_RETURN_LAUNCH(who);
   }
   if (!(flags & LNR_BWD_LEVEL_MAX_READY)) {  // (the record scales: after the MLP backward, which writes d_enc / J)
     LNR_REQUIRE(hipMemsetAsync(w.level_max, 0, LNR_MAX_LEVELS * sizeof(float), st) == hipSuccess, "%s: memset failed",
@@ -1625,13 +1584,11 @@ static int launch_bwd_bucketed(const lnr_grid_desc* d, PosFn pos, int64_t n, Gra
                 : m == 6 ? k_bwd_scatter_rows<PosFn, GradFn, 16, 6, 64>
                          : k_bwd_scatter_rows<PosFn, GradFn, 16, 7, 64>;
     hipLaunchKernelGGL(kern, dim3((unsigned)w.n_sb), dim3(kSB), 0, st, a, pos, n, grad, w, skip_zero);
-#if LNR_ROWS_NB128
   } else if (rows && m >= 5 && m <= 7 && maxnb <= 128) {  // the colour grid (2^19 entries: 128 chunks per level)
     auto kern = m == 5   ? k_bwd_scatter_rows<PosFn, GradFn, 16, 5, 128>
                 : m == 6 ? k_bwd_scatter_rows<PosFn, GradFn, 16, 6, 128>
                          : k_bwd_scatter_rows<PosFn, GradFn, 16, 7, 128>;
     hipLaunchKernelGGL(kern, dim3((unsigned)w.n_sb), dim3(kSB), 0, st, a, pos, n, grad, w, skip_zero);
-#endif
   } else {
     hipLaunchKernelGGL((k_bwd_scatter<PosFn, GradFn, kLevelsAny>), dim3((unsigned)(w.n_sb * L)), dim3(kSB), kScatterLds,
                        st, a, pos, n, grad, w, 0u, skip_zero);

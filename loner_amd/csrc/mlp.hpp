@@ -24,19 +24,6 @@ struct SigmaWeights {
   __device__ __forceinline__ half8_t BT(int m, int s) const { return bt[m][s]; }
 };
 
-// The same operands kept in LDS (one copy per workgroup, [operand][64 lanes] of 16 B: conflict-free
-// ds_read_b128) and read where used: 32 fewer registers per lane for a register-bound kernel.
-struct SigmaWeightsLds {
-  const half8_t* a0;  // [4][64]
-  const half8_t* bt;  // [2 m][2 s][64]
-  half8_t w1h[2];
-  __device__ __forceinline__ float w1(int k) const { return (float)w1h[k >> 3][k & 7]; }
-  __device__ __forceinline__ half8_t A0(int t) const { return a0[t * 64 + (threadIdx.x & 63)]; }
-  __device__ __forceinline__ half8_t BT(int m, int s) const { return bt[(2 * m + s) * 64 + (threadIdx.x & 63)]; }
-  // stage from registers (every wave writes the same values: wave 0's write suffices; the caller syncs)
-  __device__ __forceinline__ void stage(half8_t* lds, const struct SigmaWeights& sw);
-};
-
 // The hidden layer of one 16-sample tile, fp16 (tcnn stores it so): h[k] = relu(H)[hid 16t + 4g + r][sample
 // l&15] at k = 4t + r, as packed halves (8 registers, not 16)
 struct SigmaHidden {
@@ -67,22 +54,6 @@ __device__ __forceinline__ void load_sigma_weights(const uint16_t* __restrict__ 
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       sw.w1h[(4 * t + r) >> 3][(4 * t + r) & 7] = __builtin_bit_cast(_Float16, w1[16 * t + 4 * g + r]);
-}
-
-__device__ __forceinline__ void SigmaWeightsLds::stage(half8_t* lds, const SigmaWeights& sw) {
-  const int lane = threadIdx.x & 63;
-  if (threadIdx.x < 64) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) lds[t * 64 + lane] = sw.a0[t];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) lds[(4 + 2 * m + q) * 64 + lane] = sw.bt[m][q];
-  }
-  a0 = lds;
-  bt = lds + 4 * 64;
-  w1h[0] = sw.w1h[0];
-  w1h[1] = sw.w1h[1];
 }
 
 // B operand of the forward product for sample n (lane column): features 8g..8g+7 = levels 4g..4g+3.
@@ -240,69 +211,10 @@ struct DW0Mfma {
   }
 };
 
-__device__ __forceinline__ void dw0_pair_mfma(_Float16* __restrict__ lds, const SigmaHidden& h0, const SigmaHidden& h1,
-                                              const half8_t& e0, const half8_t& e1, float ds0, float ds1, float maxabs,
-                                              DW0Mfma& acc) {
-  if (!(maxabs > 0.f) || !isfinite(maxabs)) return;  // (wave-uniform) nothing to add
-  int e;
-  frexpf(maxabs, &e);
-  int k = 13 - e;
-  k = k > 100 ? 100 : (k < -100 ? -100 : k);
-  if (k < acc.kc) {  // a larger pair: the sums so far move to the smaller scale
-    if (acc.kc != DW0Mfma::kUnset) {
-      const float f = ldexpf(1.f, k - acc.kc);
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) acc.v[t][m] *= f;
-    }
-    acc.kc = k;
-  }
-  const float scale = ldexpf(1.f, acc.kc);
-  const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-  _Float16* mk = lds;             // [64 hid][32 samples] ReLU mask
-  _Float16* ens = lds + 64 * 32;  // [32 in][32 samples] scaled ds * Enc
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int kk = 8 * q + j, hid = 16 * (kk >> 2) + 4 * g + (kk & 3);
-      mk[hid * 32 + c] = h0.q[q][j] > (_Float16)0.f ? (_Float16)1.f : (_Float16)0.f;
-      mk[hid * 32 + 16 + c] = h1.q[q][j] > (_Float16)0.f ? (_Float16)1.f : (_Float16)0.f;
-    }
-  const float s0 = ds0 * scale, s1 = ds1 * scale;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-#ifdef LNR_DW0_DOUBLE_ROUND
-    float p0 = (float)e0[j] * s0, p1 = (float)e1[j] * s1;
-    asm volatile("" : "+v"(p0), "+v"(p1));
-    ens[(8 * g + j) * 32 + c] = (_Float16)p0;
-    ens[(8 * g + j) * 32 + 16 + c] = (_Float16)p1;
-#else
-    ens[(8 * g + j) * 32 + c] = (_Float16)((float)e0[j] * s0);
-    ens[(8 * g + j) * 32 + 16 + c] = (_Float16)((float)e1[j] * s1);
-#endif
-  }
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): wave-local hand-off through LDS
-  __builtin_amdgcn_wave_barrier();
-  half8_t a[4], b[2];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) a[t] = *reinterpret_cast<const half8_t*>(mk + (16 * t + c) * 32 + 8 * g);
-#pragma unroll
-  for (int m = 0; m < 2; ++m) b[m] = *reinterpret_cast<const half8_t*>(ens + (16 * m + c) * 32 + 8 * g);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc.v[t][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t], b[m], acc.v[t][m], 0, 0, 0);
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-}
-
-// dw0_pair_mfma in three parts, so a tile's hidden layer and encoding can be handed to the LDS right
-// after its own use and the two tiles are never live together (same operands, same MFMAs: bitwise
-// the same sums).  dw0_scale: the pair's operand scale from max |ds * Enc| over both tiles (an input
-// property, known before the forward), false when the pair adds nothing; dw0_stage: tile half's mask
-// and scaled ds * Enc into the wave's LDS; dw0_mfma: the 8 MFMAs once both halves are staged.
+// A pair's place in that running scale, from max |ds * Enc| over the pair's two tiles (wave-uniform; an input
+// property, known before the forward): false when the pair adds nothing (a zero or non-finite maximum), else the
+// exponent moves down to the pair's if it is the largest so far, the sums so far are rescaled with it, and
+// `scale` = 2^kc is what the caller multiplies ds * Enc by for the fp16 operand of its MFMAs into acc.v.
 __device__ __forceinline__ bool dw0_scale(float maxabs, DW0Mfma& acc, float& scale) {
   if (!(maxabs > 0.f) || !isfinite(maxabs)) return false;  // (wave-uniform) nothing to add
   int e;
@@ -321,39 +233,6 @@ __device__ __forceinline__ bool dw0_scale(float maxabs, DW0Mfma& acc, float& sca
   }
   scale = ldexpf(1.f, acc.kc);
   return true;
-}
-__device__ __forceinline__ void dw0_stage(_Float16* __restrict__ lds, int half, const SigmaHidden& h, const half8_t& e,
-                                          float ds_scaled) {
-  const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-  _Float16* mk = lds + 16 * half;
-  _Float16* ens = lds + 64 * 32 + 16 * half;
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int kk = 8 * q + j, hid = 16 * (kk >> 2) + 4 * g + (kk & 3);
-      mk[hid * 32 + c] = h.q[q][j] > (_Float16)0.f ? (_Float16)1.f : (_Float16)0.f;
-    }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) ens[(8 * g + j) * 32 + c] = (_Float16)((float)e[j] * ds_scaled);
-}
-__device__ __forceinline__ void dw0_mfma(const _Float16* __restrict__ lds, DW0Mfma& acc) {
-  const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-  const _Float16* mk = lds;
-  const _Float16* ens = lds + 64 * 32;
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): wave-local hand-off through LDS
-  __builtin_amdgcn_wave_barrier();
-  half8_t a[4], b[2];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) a[t] = *reinterpret_cast<const half8_t*>(mk + (16 * t + c) * 32 + 8 * g);
-#pragma unroll
-  for (int m = 0; m < 2; ++m) b[m] = *reinterpret_cast<const half8_t*>(ens + (16 * m + c) * 32 + 8 * g);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc.v[t][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t], b[m], acc.v[t][m], 0, 0, 0);
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
 }
 
 // Block-level write of the per-block dW slab (3072 fp32, layout W0 (64,32) then W1 (16,64)).

@@ -440,16 +440,10 @@ __global__ void __launch_bounds__(64 * kSamplerWaves) k_sampler_wave(SamplerArgs
 #ifndef LNR_GALLOP_JT
 #define LNR_GALLOP_JT 1
 #endif
-#ifndef LNR_GALLOP_CDF
-#define LNR_GALLOP_CDF 0
-#endif
 #ifndef LNR_SAMPLER_MERGE_FILL
 // the merge places the depths (each one's stratum count from the linspace, corrected by a short walk: no chain
 // of searches) and fills the other positions with the strata in order (a mark per position, a wave scan)
 #define LNR_SAMPLER_MERGE_FILL 1
-#endif
-#ifndef LNR_SAMPLER_CDF_LIFT
-#define LNR_SAMPLER_CDF_LIFT 1
 #endif
 #ifndef LNR_SAMPLER_LOOKUP_UNROLL
 #define LNR_SAMPLER_LOOKUP_UNROLL 4
@@ -462,7 +456,7 @@ __global__ void __launch_bounds__(64 * kSamplerWaves) k_sampler_wave(SamplerArgs
 // VALU work).  Then:
 //  * counting sort of the H draws into 2H buckets (LDS atomics, a wave scan), the few bucket mates put in
 //    order by odd-even transposition passes in registers;
-//  * the inverse CDF per sorted draw, its searchsorted answer walked on from the previous draw's;
+//  * the inverse CDF per sorted draw, its searchsorted answer by binary lifting (upper_count_lift);
 //  * strata and importance depths merged by rank: stratum i goes to i + #{importance depths < it}, depth j
 //    to j + #{strata <= it} (positions unique; equal values are interchangeable);
 //  * if the strata are not ascending (jitter rounding, checked as k_sampler_wave does) or the mapped depths
@@ -700,16 +694,12 @@ __global__ void __launch_bounds__(64 * kSamplerWaves) k_sampler_rank(SamplerArgs
     LNR_STAMP(t3);
     // 4. inverse CDF of the sorted draws (searchsorted(cdf, u, right=True) over [0, H - 1])
     float fq[Q];
-    int lo = 0;
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       const float u = su[q];
-      // the previous draw's answer, or the first cdf entry above u after it (the answer capped at H - 1)
-      // (LNR_SAMPLER_CDF_LIFT: each draw's search from scratch, fixed steps, so the Q searches overlap; else
-      // walked on from the previous draw's answer)
-      lo = LNR_SAMPLER_CDF_LIFT ? upper_count_lift<H - 1>(cdf, u)
-           : LNR_GALLOP_CDF     ? gallop_from<true>(cdf, lo, H - 1, u)
-                                : upper_bound_from(cdf, lo, H - 1, u);
+      // the first cdf entry above u (the answer capped at H - 1), each draw's search from scratch in a fixed number
+      // of steps, so the lane's Q searches overlap their LDS reads
+      const int lo = upper_count_lift<H - 1>(cdf, u);
       const int below = lo - 1 > 0 ? lo - 1 : 0;
       const int above = lo < M ? lo : M;
       const float c0 = cdf[below], c1 = cdf[above];

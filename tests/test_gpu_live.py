@@ -60,7 +60,7 @@ def _records(L, eng):
 @pytest.mark.parametrize("fused", [False, True])
 def test_live_backward_bitwise_on_trained_field(trained, fused):
     """Full backward without early ray termination (the reference's arithmetic) against the live backward, early ray
-    termination (LONER_ERT, csrc/field.hip kErtTMin: the rays whose transmittance fell below 1e-100 skip the encode
+    termination (LONER_ERT, csrc/field.hip kErtTMin: the rays whose transmittance fell below 1e-50 skip the encode
     and sigma of their later samples) and both, eager and graph-replayed: bitwise equal."""
     from loner_amd import _lib as L
     from loner_amd import step as S_

@@ -56,6 +56,7 @@ def _timed_rows(paths_mults, warmup):
     return max(n_steps or 0, 1), out
 
 
+# (the second: round 1's fused forward + compositing kernel, since removed; named so that its profiles still parse)
 MLP_KERNELS = ("k_sigma_fwd_tiles", "k_field_wave", "k_mlp_bwd_tiles")
 N_SIMD = 256 * 4  # 256 CUs x 4 SIMDs
 
