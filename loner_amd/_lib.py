@@ -4,244 +4,164 @@ The library is built in-tree by ``python -m loner_amd.build`` (or ``__graft_entr
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised —
 mirroring tiny-cuda-nn's ``CHECK_THROW`` behaviour at the same boundary.
 
+The binding is read from the header at import (``parse_header``); nothing of the ABI is restated here.
+  - ``#define LNR_X <expr>`` becomes the module constant ``X``.  ``<expr>`` holds integer and float literals
+    (``u`` suffix allowed), ``INT64_MAX``, earlier ``LNR_`` names and ``+ - * << ( )``, nothing else.
+    ``LOSS_KINDS``, ``RENDER_STRATEGIES`` and ``SELECT`` are the ``LNR_LOSS_*``, ``LNR_RENDER_*`` and ``LNR_SELECT_*``
+    groups.
+  - ``typedef struct lnr_x {...} lnr_x;`` becomes a ``ctypes.Structure`` (``lnr_grid_desc`` -> ``GridDesc``): the
+    fields in order, fixed-width scalars by ``_SCALARS``, ``name[expr]`` an array, an earlier ``lnr_`` struct by value.
+  - ``ret lnr_name(params);`` gives the function's restype and argtypes (``FUNCTIONS``); ``int`` is also a scalar here.
+  - Every pointer is ``c_void_p`` (device tensors, ``byref(struct)`` and struct arrays in device memory all pass
+    through it); a ``const char*`` return is ``c_char_p``.
+  - A line that fits none of these is an error naming the line, never skipped.
+
 torch is imported before the library is loaded so that the library binds to the HIP runtime
 torch already loaded (one runtime per process; streams are shared).
 """
+import collections
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "libloner_amd.so")
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "_lib", "libloner_amd.so")
 # Kernel experiments load an alternative in-tree build (tools/exp_variants.py); unset in production.
 LIB_PATH = os.environ.get("LONER_AMD_LIB", LIB_PATH)
-MAX_LEVELS = 32
-RAY_STATS = 5
-SIGMA_MLP_PARAMS = 64 * 32 + 16 * 64
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "loner_amd.h")
 
-LOSS_KINDS = {"L1_JS": 0, "L2_JS": 1, "L1_LOS": 2, "L2_LOS": 3}
-RENDER_STRATEGIES = {"default": 0, "adjusted": 1}
-BWD_COUNTS_READY = 1
-BWD_NO_ACCUM = 2
-BWD_LEVEL_MAX_READY = 4
-BWD_LIVE = 8  # the live backward: records only for samples with d_sigma != 0 (bitwise the full one)
-BWD_PREPARE_ONLY = 16  # stop before the scatter (histogram + scans); needs BWD_LIVE or BWD_COUNTS_READY
-BWD_PREPARED = 32  # a BWD_PREPARE_ONLY call with the same arguments ran
+_SCALARS = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+_PROTO_SCALARS = dict(_SCALARS, int=ctypes.c_int)
+_CLASS_NAMES = {"lnr_ray_window": "RayWindowDesc"}  # loner_amd.rays.RayWindow is the class that fills it
 
-c_p = ctypes.c_void_p
-c_i64 = ctypes.c_int64
-c_i32 = ctypes.c_int32
-c_u32 = ctypes.c_uint32
-c_f = ctypes.c_float
-c_d = ctypes.c_double
+Header = collections.namedtuple("Header", "constants structs functions")
+# ret and params hold the C spelling: "const char*", [("const lnr_loss_params*", "lp"), ...]
+Function = collections.namedtuple("Function", "restype argtypes ret params")
 
-
-class GridDesc(ctypes.Structure):
-    _fields_ = [("n_levels", ctypes.c_uint32), ("n_features", ctypes.c_uint32),
-                ("log2_hashmap_size", ctypes.c_uint32), ("base_resolution", ctypes.c_uint32),
-                ("per_level_scale", ctypes.c_float), ("n_entries", ctypes.c_uint32),
-                ("scale", ctypes.c_float * MAX_LEVELS), ("resolution", ctypes.c_uint32 * MAX_LEVELS),
-                ("size", ctypes.c_uint32 * MAX_LEVELS), ("offset", ctypes.c_uint32 * (MAX_LEVELS + 1))]
+_TOKEN = re.compile(r"\s*(?:(0[xX][0-9a-fA-F]+|\d+(?:\.\d*)?(?:[eE][-+]?\d+)?)[uU]?|(LNR_\w+|INT64_MAX)|(<<|[-+*()]))")
+_SPACE = re.compile(r"\s*")
+_PREPROCESSOR = re.compile(r"#\s*(?:(?:ifndef|ifdef|endif|include)\b.*|define\s+(?!LNR_)\w+)")
+_DEFINE = re.compile(r"#\s*define\s+LNR_(\w+)\s+(\S.*)")
+_EXTERN_C = re.compile(r'extern\s+"C"\s*\{|\}')
+_TYPE = r"((?:const\s+)?\w+)"
+_STRUCT = re.compile(r"typedef\s+struct\s+(lnr_\w+)\s*\{(.*?)\}\s*(\w+)\s*;", re.S)
+_FIELD = re.compile(_TYPE + r"\b(.*)", re.S)
+_DECLARATOR = re.compile(r"\s*(\**)\s*(\w+)\s*(?:\[([^\[\]]+)\])?\s*")
+_PROTO = re.compile(_TYPE + r"\s*(\**)\s*(lnr_\w+)\s*\(([^()]*)\)\s*;")
+_PARAM = re.compile(r"\s*" + _TYPE + r"(\s*\*+\s*|\s+)(\w+)\s*")
 
 
-class StepScalars(ctypes.Structure):
-    """``lnr_step_scalars``: the per-step scalars a captured step reads from device memory."""
-    _fields_ = [("key", ctypes.c_uint32), ("los_lambda", ctypes.c_float), ("los_eps", ctypes.c_float),
-                ("adam_step_size", ctypes.c_float), ("adam_bc2_sqrt", ctypes.c_float), ("pad", ctypes.c_uint32 * 3)]
+def parse_header(path=HEADER_PATH):
+    """The constants, structs and functions ``path`` declares (module docstring); RuntimeError on anything else."""
+    if not os.path.exists(path):
+        raise RuntimeError(f"loner_amd: C header not found ({path})")
+    with open(path) as f:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", lambda m: "\n" * m.group().count("\n"), f.read(), flags=re.S)
+    constants, structs, functions = {}, {}, {}
+
+    def error(offset, what):
+        line = text.count("\n", 0, offset) + 1
+        return RuntimeError(f"{path}:{line}: {what}: {text.splitlines()[line - 1].strip()!r}")
+
+    def evaluate(expr, offset):
+        names, terms, pos = dict(constants, INT64_MAX=2 ** 63 - 1), [], 0
+        while pos < len(expr.rstrip()):
+            m = _TOKEN.match(expr, pos)
+            if not m or (m.group(2) and m.group(2).replace("LNR_", "", 1) not in names):
+                raise error(offset, f"unsupported constant expression {expr.strip()!r}")
+            number, name, operator = m.groups()
+            terms.append(f"({names[name.replace('LNR_', '', 1)]!r})" if name else number or operator)
+            pos = m.end()
+        try:
+            return eval(" ".join(terms), {"__builtins__": {}})  # literals and + - * << ( ) only, checked above
+        except Exception:
+            raise error(offset, f"unsupported constant expression {expr.strip()!r}") from None
+
+    def ctype(base, stars, scalars, offset, ret=False):
+        if stars:
+            return ctypes.c_char_p if ret and base == "const char" else ctypes.c_void_p
+        if base not in scalars:
+            raise error(offset, f"unknown type {base!r}")
+        return scalars[base]
+
+    def struct(m):
+        name, body, alias = m.groups()
+        fields = []
+        for decl in re.finditer(r"[^;]*[^;\s][^;]*;", body):
+            offset = m.start(2) + decl.start() + len(decl.group()) - len(decl.group().lstrip())
+            f = _FIELD.fullmatch(decl.group()[:-1].strip())
+            declarators = [_DECLARATOR.fullmatch(d) for d in f.group(2).split(",")] if f else [None]
+            if not all(declarators):
+                raise error(offset, "unrecognised struct field")
+            for d in declarators:
+                t = ctype(f.group(1), d.group(1), dict(_SCALARS, **structs), offset)
+                fields.append((d.group(2), t * evaluate(d.group(3), offset) if d.group(3) else t))
+        if alias != name or not body.rstrip().endswith(";"):
+            raise error(m.start(), "unrecognised struct")
+        py_name = _CLASS_NAMES.get(name) or "".join(w.capitalize() for w in name.split("_")[1:])
+        structs[name] = type(py_name, (ctypes.Structure,), {"_fields_": fields})
+
+    def prototype(m):
+        base, stars, name, params = m.groups()
+        restype = ctype(base, stars, _PROTO_SCALARS, m.start(), ret=True)
+        argtypes, c_params = [], []
+        for p in re.finditer(r"[^,]+", "" if params.strip() == "void" else params):
+            offset = m.start(4) + p.start() + len(p.group()) - len(p.group().lstrip())
+            pm = _PARAM.fullmatch(p.group())
+            if not pm:
+                raise error(offset, "unrecognised parameter")
+            argtypes.append(ctype(pm.group(1), pm.group(2).strip(), _PROTO_SCALARS, offset))
+            c_params.append((pm.group(1) + pm.group(2).strip(), pm.group(3)))
+        if params.strip() != "void" and len(argtypes) != params.count(",") + 1:
+            raise error(m.start(), "unrecognised parameter list")
+        functions[name] = Function(restype, argtypes, base + stars, c_params)
+
+    pos = 0
+    while True:
+        pos = _SPACE.match(text, pos).end()
+        if pos == len(text):
+            break
+        if text[pos] == "#":
+            end = text.find("\n", pos) % (len(text) + 1)  # no newline: the text's end
+            line = text[pos:end].rstrip()
+            m = _DEFINE.fullmatch(line)
+            if m:
+                constants[m.group(1)] = evaluate(m.group(2), pos)
+            elif not _PREPROCESSOR.fullmatch(line):
+                raise error(pos, "unrecognised preprocessor line")
+            pos = end
+            continue
+        for pattern, handle in ((_EXTERN_C, None), (_STRUCT, struct), (_PROTO, prototype)):
+            m = pattern.match(text, pos)
+            if m:
+                if handle:
+                    handle(m)
+                pos = m.end()
+                break
+        else:
+            raise error(pos, "unrecognised declaration")
+    mentioned = re.findall(r"\b(lnr_\w+)\s*\(", re.sub(r"\{[^{}]*\}", "", text))
+    if sorted(mentioned) != sorted(functions):
+        raise RuntimeError(f"{path}: functions named but not parsed once each: {set(mentioned) ^ set(functions)}")
+    return Header(constants, structs, functions)
 
 
-class AdamRange(ctypes.Structure):
-    """lnr_adam_range (include/loner_amd.h)."""
-    _fields_ = [("param", ctypes.c_void_p), ("shadow", ctypes.c_void_p), ("grad", ctypes.c_void_p),
-                ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("n", ctypes.c_int64)]
+_header = parse_header()
+CONSTANTS, STRUCTS, FUNCTIONS = _header
+globals().update(CONSTANTS)
+globals().update({cls.__name__: cls for cls in STRUCTS.values()})
 
 
-ADAM_MAX_RANGES = 8
+def _group(prefix, key=str):
+    return {key(k[len(prefix):]): v for k, v in CONSTANTS.items() if k.startswith(prefix)}
 
 
-class AdamEpilogue(ctypes.Structure):
-    """lnr_adam_epilogue (include/loner_amd.h): Adam fused into the hash-grid backward."""
-    _fields_ = [("param", ctypes.c_void_p), ("shadow", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
-                ("step", ctypes.c_int32), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
-                ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("dev_step", ctypes.c_void_p)]
-
-
-class LossParams(ctypes.Structure):
-    _fields_ = [("kind", ctypes.c_int32), ("scale", ctypes.c_float), ("los_lambda", ctypes.c_float),
-                ("depthloss_lambda", ctypes.c_float), ("min_depth_eps", ctypes.c_float),
-                ("min_js", ctypes.c_float), ("max_js", ctypes.c_float), ("js_alpha", ctypes.c_float),
-                ("los_eps", ctypes.c_float), ("far_ref", ctypes.c_float), ("inv_n_opaque", ctypes.c_float),
-                ("inv_rs", ctypes.c_float), ("dev_n_opaque", ctypes.c_void_p), ("dev_far_ref", ctypes.c_void_p),
-                ("dev_status", ctypes.c_void_p), ("dev_loss_out", ctypes.c_void_p), ("flags", ctypes.c_int32),
-                ("dev_step", ctypes.c_void_p), ("dev_d_ray", ctypes.c_void_p), ("dev_term_hist", ctypes.c_void_p)]
-
-
-LP_DW_OVERWRITE = 1
-LP_SIGMA_READY = 2
-LP_FORWARD_ONLY = 4
-LP_BACKWARD_ONLY = 8
-ERT_T_MIN = 1e-50  # LNR_ERT_T_MIN
-
-
-STATUS_NAN_LOSS, STATUS_INF_LOSS, STATUS_SIGMA_CLIPPED, STATUS_NONFINITE_OUTPUT = 1, 2, 4, 8
-
-
-CLOUD_NONFINITE, CLOUD_GRID_RANGE = 1, 2  # LNR_CLOUD_* status bits
-CLOUD_BAD_KEY = 2 ** 63 - 1
-CLOUD_CELL_BITS = 21
-CLOUD_VOXEL_CHUNK = 64
-
-SELECT = {"RANDOM": 0, "MASK": 1, "ALL": 2, "GIVEN": 3}
-
-
-class RayWindowDesc(ctypes.Structure):
-    """``lnr_ray_window``: device pointers of a resident keyframe window (loner_amd.rays.RayWindow)."""
-    _fields_ = [("n_kf", ctypes.c_int32), ("scale", ctypes.c_float), ("shift", ctypes.c_float * 3),
-                ("r_min", ctypes.c_float), ("r_max", ctypes.c_float), ("poses", c_p), ("dirs", c_p), ("dists", c_p),
-                ("scan_off", c_p), ("order", c_p), ("n_trunk", c_p), ("sky_dirs", c_p), ("sky_off", c_p),
-                ("ray_off", c_p), ("n_sel", c_p), ("n_sel_trunk", c_p), ("dev_step", c_p)]
-
-
-class MotionComp(ctypes.Structure):
-    """``lnr_motion_comp``."""
-    _fields_ = [("start_rot", ctypes.c_float * 9), ("start_t", ctypes.c_float * 3), ("delta_t", ctypes.c_float * 3),
-                ("axis", ctypes.c_float * 3), ("angle", ctypes.c_float), ("t0", ctypes.c_float), ("t1", ctypes.c_float),
-                ("target_inv", ctypes.c_float * 12), ("identity", ctypes.c_int32)]
-
-
-class CameraDesc(ctypes.Structure):
-    """``lnr_camera_desc``."""
-    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("channels", ctypes.c_int32),
-                ("scale", ctypes.c_float), ("shift", ctypes.c_float * 3), ("r_min", ctypes.c_float),
-                ("pose", ctypes.c_float * 12)]
-
-
-class CameraFrame(ctypes.Structure):
-    """``lnr_camera_frame``."""
-    _fields_ = [("cam", CameraDesc), ("image", ctypes.c_void_p)]
-
-
-class SkyParams(ctypes.Structure):
-    """``lnr_sky_params``."""
-    _fields_ = [("rot", ctypes.c_float * 9), ("top_rows", ctypes.c_int32), ("horizon_deg", ctypes.c_float)]
-
-
-class IcpState(ctypes.Structure):
-    """``lnr_icp_state``: the device-resident state of the ICP schedule."""
-    _fields_ = [("T", ctypes.c_double * 16), ("fitness", ctypes.c_double), ("rmse", ctypes.c_double),
-                ("sum_d2", ctypes.c_double), ("sums", ctypes.c_double * 27), ("n_corr", ctypes.c_int64),
-                ("iterations", ctypes.c_int32), ("converged", ctypes.c_int32)]
-
-
-_SIGNATURES = {
-    "lnr_version": (ctypes.c_int, []),
-    "lnr_last_error": (ctypes.c_char_p, []),
-    "lnr_grid_desc_init": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_u32, c_u32, c_u32, c_u32, c_f]),
-    "lnr_hashgrid_fwd": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p]),
-    "lnr_hashgrid_fwd_rays": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64, c_p,
-                                             c_i64, c_p]),
-    "lnr_hashgrid_bwd_workspace_bytes": (c_i64, [ctypes.POINTER(GridDesc), c_i64]),
-    "lnr_hashgrid_bwd_level_max": (c_p, [ctypes.POINTER(GridDesc), c_i64, c_p]),
-    "lnr_hashgrid_bwd_seg_start": (c_p, [ctypes.POINTER(GridDesc), c_i64, c_p]),
-    "lnr_hashgrid_bwd": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
-                                        c_i32, c_p]),
-    "lnr_hashgrid_bwd_rays": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p,
-                                             c_p, c_p, c_i64, c_i32, c_p]),
-    "lnr_hashgrid_bwd_rays_jac": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64,
-                                                 c_p, c_p, c_p, c_p, c_i64, c_i32, c_p]),
-    "lnr_hashgrid_bwd_rays_jac_adam": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64,
-                                                      ctypes.POINTER(AdamEpilogue), c_p, c_i64, c_i32, c_p]),
-    "lnr_hashgrid_bwd_accum": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_i64, c_p, c_i64, c_u32, c_u32, c_p, c_p]),
-    "lnr_hashgrid_bwd_accum_flags": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_i64, c_p, c_i64, c_u32, c_u32, c_p,
-                                                     ctypes.c_int32, c_p]),
-    "lnr_hashgrid_bwd_atomic": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_i64, c_p, c_i64, c_p, c_p]),
-    "lnr_hashgrid_bwd_rays_atomic": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p,
-                                                    c_p]),
-    "lnr_enc_to_aos": (ctypes.c_int, [c_p, c_i64, c_i64, c_u32, c_p, c_p]),
-    "lnr_aos_grad_to_enc": (ctypes.c_int, [c_p, c_p, c_i64, c_u32, c_p, c_i64, c_p]),
-    "lnr_sh_encode": (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_p]),
-    "lnr_sigma_mlp_fwd": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_p, c_p]),
-    "lnr_dw_workspace_words": (c_i64, [c_i64]),
-    "lnr_field_train_workspace_words": (c_i64, [c_i64, c_i32]),
-    "lnr_sigma_mlp_bwd": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
-    "lnr_step_key": (c_u32, [c_u32, c_u32]),
-    "lnr_sample_ogm": (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_i32, c_f, c_p, c_p, c_u32, c_i64, c_p, c_p, c_p]),
-    "lnr_sample_uniform": (ctypes.c_int, [c_p, c_i64, c_i32, c_f, c_p, c_u32, c_i64, c_p, c_p, c_p]),
-    "lnr_composite": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i32, c_f, c_p, c_u32, c_i64, c_p, c_p, c_p, c_p,
-                                     c_p]),
-    "lnr_composite_bwd": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i32, c_f, c_p, c_u32, c_i64, c_p, c_p, c_p,
-                                         c_p, c_p, c_p, c_p]),
-    "lnr_composite_loss_bwd": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i32, c_f, c_p, c_u32, c_i64,
-                                              ctypes.POINTER(LossParams), c_p, c_p, c_p, c_p, c_p, c_p]),
-    "lnr_field_train": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i32, c_f, c_p, c_u32, c_i64,
-                                       ctypes.POINTER(LossParams), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                       c_p]),
-    "lnr_field_sigma_phase": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_f, c_p, c_u32,
-                                             c_i64, ctypes.POINTER(LossParams), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "lnr_field_ert_march": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i32, c_i32,
-                                           c_f, c_p, c_u32, c_i64, ctypes.POINTER(LossParams), c_p, c_p, c_p, c_p,
-                                           c_p]),
-    "lnr_pose_grad": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p, c_p, c_i32, c_f, c_f, c_p,
-                                     c_p, c_p]),
-    "lnr_pose_adam": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i64, c_d, c_d, c_d, c_d, c_p, c_p]),
-    "lnr_field_render": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_i32, c_i32, c_f, c_p, c_u32, c_i64, c_p,
-                                        c_p, c_p, c_p, c_p]),
-    "lnr_rgb_render": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_p, c_p, c_i64, c_i32, c_p, c_p]),
-    "lnr_hashgrid_fwd_rays_phase": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64,
-                                                   c_p, c_i64, c_p, c_p, c_i64, c_i32, c_i32, c_p]),
-    "lnr_hashgrid_fwd_rays_live": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_i64,
-                                                  c_p]),
-    "lnr_hashgrid_fwd_rays_live_ws": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_p, c_p,
-                                                     c_i64, c_p, c_i64, c_p]),
-    "lnr_hashgrid_bwd_rays_live": (ctypes.c_int, [ctypes.POINTER(GridDesc), c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p,
-                                                  c_p, c_i64, c_i32, c_p]),
-    "lnr_status_scan": (ctypes.c_int, [c_p, c_i64, c_u32, c_p, c_p]),
-    "lnr_rgb_mlp_params": (c_i64, [c_i32]),
-    "lnr_rgb_train_workspace_bytes": (c_i64, [c_i32, c_i64]),
-    "lnr_rgb_train": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i32, c_f, c_p, c_p, c_p, c_p,
-                                     c_p, c_i64, c_p, c_p]),
-    "lnr_build_camera_rays": (ctypes.c_int, [ctypes.POINTER(CameraDesc), c_p, c_p, c_p, c_i64, c_p, c_p, c_p]),
-    "lnr_build_camera_rays_window": (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "lnr_motion_compensate": (ctypes.c_int, [ctypes.POINTER(MotionComp), c_p, c_p, c_p, c_i64, c_p]),
-    "lnr_sky_rays_capacity": (c_i64, []),
-    "lnr_sky_rays": (ctypes.c_int, [c_p, c_i64, ctypes.POINTER(SkyParams), c_p, c_i64, c_p, c_p]),
-    "lnr_loss_finalize": (ctypes.c_int, [c_p, c_i64, ctypes.POINTER(LossParams), c_p, c_p]),
-    "lnr_count_opaque": (ctypes.c_int, [c_p, c_i64, c_f, c_p, c_p, c_p]),
-    "lnr_build_lidar_rays": (ctypes.c_int, [ctypes.POINTER(RayWindowDesc), c_i32, c_p, c_u32, c_i64, c_i64, c_p, c_p,
-                                            c_p, c_p, c_p, c_p]),
-    "lnr_adam_step": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_d, c_d, c_d, c_d, c_p, c_p]),
-    "lnr_adam_step_ranges": (ctypes.c_int, [c_p, c_i32, c_i32, c_d, c_d, c_d, c_d, c_p, c_p]),
-    "lnr_step_scalars_set": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),
-    "lnr_adam_coefficients": (ctypes.c_int, [c_i32, c_d, c_d, c_d, ctypes.POINTER(c_f), ctypes.POINTER(c_f)]),
-    "lnr_ogm_workspace_words": (c_i64, [c_i32]),
-    "lnr_ogm_update": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_f, c_f, c_p, c_p, c_i64, c_i32, c_p]),
-    "lnr_ogm_grad": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_f, c_p, c_i64, c_i32, c_p]),
-    "lnr_grid_sample3d": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_p, c_p]),
-    "lnr_grid_sample3d_bwd_workspace_words": (c_i64, [c_i32]),
-    "lnr_grid_sample3d_bwd": (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64, c_p]),
-    "lnr_sgd_step": (ctypes.c_int, [c_p, c_p, c_i64, c_f, c_p]),
-    "lnr_volume_splat_max": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p, c_i32, c_p, c_i32, c_p, c_i32,
-                                            c_f, c_f, c_p, c_p]),
-    "lnr_marching_cubes_count": (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_f, c_p, c_p, c_p]),
-    "lnr_marching_cubes_emit": (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f, c_p, c_p, c_i64, c_i64,
-                                               c_p, c_p, c_p]),
-    "lnr_cloud_normals": (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_p]),
-    "lnr_icp_workspace_bytes": (c_i64, [c_i64]),
-    "lnr_icp_init": (ctypes.c_int, [c_p, ctypes.POINTER(c_d), c_p]),
-    "lnr_icp_stage": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_f, c_i32, c_d, c_d, c_p, c_p, c_i64, c_p, c_p,
-                                     c_p]),
-    "lnr_cloud_cell_keys": (ctypes.c_int, [c_p, c_i64, c_p, c_d, c_p, c_p, c_p]),
-    "lnr_voxel_heads": (ctypes.c_int, [c_p, c_i64, c_p, c_p]),
-    "lnr_voxel_workspace_bytes": (c_i64, [c_i64, c_i64]),
-    "lnr_voxel_reduce": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p]),
-    "lnr_nn_workspace_bytes": (c_i64, [c_i64]),
-    "lnr_nn_search": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_d, c_p, c_p, c_i64, c_p, c_p, c_p, c_p,
-                                     c_p]),
-    "lnr_dist_stats_workspace_bytes": (c_i64, [c_i64]),
-    "lnr_dist_stats": (ctypes.c_int, [c_p, c_i64, c_d, c_p, c_i64, c_p, c_p]),
-    "lnr_fill_uniform": (ctypes.c_int, [c_p, c_i64, c_u32, c_f, c_f, c_i64, c_p]),
-    "lnr_f32_to_f16": (ctypes.c_int, [c_p, c_p, c_i64, c_p]),
-}
+LOSS_KINDS = _group("LOSS_")
+RENDER_STRATEGIES = _group("RENDER_", str.lower)
+SELECT = _group("SELECT_")
 
 _lib = None
 
@@ -253,10 +173,10 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"loner_amd: HIP library not built ({LIB_PATH}); run `python -m loner_amd.build`")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, f in FUNCTIONS.items():
             fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype = f.restype
+            fn.argtypes = f.argtypes
         _lib = L
     return _lib
 
@@ -272,9 +192,22 @@ def call(name, *args):
     referenced for the duration of the call; afterwards the caching allocator's stream ordering
     keeps their memory valid for the enqueued kernels."""
     conv = [ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
-    rc = getattr(lib(), name)(*conv)
+    try:
+        rc = getattr(lib(), name)(*conv)
+    except ctypes.ArgumentError as e:
+        raise _named(name, e) from None
     check(rc, name)
     return rc
+
+
+def _named(name, e):
+    """ctypes' "argument 13: TypeError: wrong type" with the function and the parameter's C declaration."""
+    m = re.match(r"argument (\d+): (.*)", str(e), re.S)
+    params = FUNCTIONS[name].params
+    if not m or not 1 <= int(m.group(1)) <= len(params):
+        return e
+    c_type, c_name = params[int(m.group(1)) - 1]
+    return ctypes.ArgumentError(f"{name}: argument {m.group(1)} ({c_type} {c_name}): {m.group(2)}")
 
 
 def ptr(t):
@@ -293,7 +226,7 @@ def stream(device=None):
 
 
 def grid_desc(n_levels=16, n_features=2, log2_hashmap_size=18, base_resolution=16, per_level_scale=2.0):
-    d = GridDesc()
+    d = GridDesc()  # noqa: F821  (lnr_grid_desc, from the header)
     check(lib().lnr_grid_desc_init(ctypes.byref(d), n_levels, n_features, log2_hashmap_size, base_resolution,
                                    per_level_scale), "lnr_grid_desc_init")
     return d
@@ -304,4 +237,4 @@ def step_key(seed, step):
 
 
 def exported_symbols():
-    return sorted(_SIGNATURES)
+    return sorted(FUNCTIONS)

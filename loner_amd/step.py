@@ -188,7 +188,6 @@ AR_CUT_DEFAULT = 6
 # 168 us exposed at 200 GB/s if the two share the link bandwidth, 148 us if not, against 191 / 156 at cut 6
 # (tools/zero_tail_model.py, profiles/r06_zero_tail_model_C4s8.txt)
 AR_CUT_TWO_GROUPS = 8
-TERM_HIST_SLOTS = 256  # LNR_TERM_HIST_SLOTS
 
 
 def _env_on(name):
@@ -450,9 +449,9 @@ class StepEngine:
         self.ert_T = torch.ones(n_rays, dtype=torch.float64, device=dev)
         self.ert_keep = torch.zeros(max(n_rays, 1), dtype=torch.int32, device=dev)
         nb = self.S // 64 + 1
-        self.term_hist = (torch.zeros(TERM_HIST_SLOTS, nb, dtype=torch.int32, device=dev) if self.S % 64 == 0
+        self.term_hist = (torch.zeros(L.TERM_HIST_SLOTS, nb, dtype=torch.int32, device=dev) if self.S % 64 == 0
                           else None)  # (slots spread the compositing's atomics; ert_probe sums them)
-        self._term_read = (_Readback((TERM_HIST_SLOTS, nb), torch.int32, self.live_probe_every)
+        self._term_read = (_Readback((L.TERM_HIST_SLOTS, nb), torch.int32, self.live_probe_every)
                            if self.term_hist is not None else None)
 
     ert, ert_cuts, ert_march = _planner_attr("mode"), _planner_attr("cuts"), _planner_attr("march")
