@@ -31,6 +31,9 @@
  *   lnr_cloud_cell_keys / lnr_voxel_heads / lnr_voxel_reduce / lnr_nn_search / lnr_dist_stats
  *                                 Open3D's voxel_down_sample and compute_point_cloud_distance, and the metric sums
  *                                 analysis/evaluate_lidar_map.py:16-81, analysis/renderer_lidar.py:292-349
+ *   lnr_mesh_face_areas / lnr_mesh_sample_points / lnr_mesh_vertex_normals
+ *                                 Open3D's sample_points_uniformly and compute_vertex_normals
+ *                                 analysis/compute_metrics/maps/mesh_to_pcd.py:21-27, analysis/meshing.py:122
  *
  * Conventions:
  *   - all data pointers are DEVICE pointers owned by the caller (PyTorch); no allocation, no host
@@ -759,6 +762,47 @@ int lnr_nn_search(const float* src, int64_t n_src, const float* tgt_sorted, cons
 int64_t lnr_dist_stats_workspace_bytes(int64_t n);
 int lnr_dist_stats(const double* dist, int64_t n, double threshold, void* workspace, int64_t ws_bytes, double* out,
                    void* stream);
+
+/* ---------------------------------------------------------------- mesh sampling (analysis/compute_metrics/maps/mesh_to_pcd.py) */
+/* A triangle mesh as a cloud (Open3D's sample_points_uniformly) and its vertex normals (compute_vertex_normals,
+ * analysis/meshing.py:122).  verts (n_verts, 3) fp32, faces (n_faces, 3) int32; 1 <= n_verts < 2^31,
+ * 1 <= n_faces <= LNR_CLOUD_MAX_POINTS.  status: 1 device uint32, ORed into and never cleared here.  A face with an
+ * index outside [0, n_verts) ORs LNR_MESH_BAD_INDEX and counts as a face of area 0; its indices are never followed.
+ * All geometry is fp64 from the fp32 vertices, every operation rounded once, in the order written here, so a float64
+ * restatement gives the same bits (loner_amd/mesh_cloud.py).  Scans and sorts between the calls are the caller's.
+ * No float atomics; every result repeats bit for bit. */
+#define LNR_MESH_BAD_INDEX 1u               /* status: a face index fell outside [0, n_verts) */
+#define LNR_MESH_NO_FACE 2u                 /* status: a point index at or above bounds[n_faces - 1] */
+/* c = e1 x e2 with e1 = v1 - v0, e2 = v2 - v0: c = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x);
+ * |c| = sqrt((cx cx + cy cy) + cz cz); area[f] = 0.5 |c| (fp64; Open3D's GetTriangleArea); normal (n_faces, 3) fp32,
+ * when not NULL: c / |c| rounded to fp32, (0, 0, 1) when |c| = 0. */
+int lnr_mesh_face_areas(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, double* area,
+                        float* normal, uint32_t* status, void* stream);
+/* The points with global indices i in [first, first + count), to points[i - first] (count, 3) fp32 and, when not NULL,
+ * their faces to face_of[i - first] (int32).  bounds (n_faces int64, non-decreasing): face t owns the points
+ * [bounds[t - 1], bounds[t]), so point i lies on the first face with bounds[t] > i and a face of zero area
+ * (bounds[t] = bounds[t - 1]) gets none.  Open3D's allocation is bounds[t] = floor(cum[t] / cum[n_faces - 1] N + 0.5),
+ * cum the inclusive fp64 scan of the areas: stratified over the area's cdf, not multinomial.  An i >= bounds[n_faces - 1]
+ * ORs LNR_MESH_NO_FACE and a point whose face has a bad index LNR_MESH_BAD_INDEX; both get a zero point and face -1.
+ * The draws are r1 = U(key, stream 7, i, 0) and r2 = U(key, stream 7, i, 1) of the counter generator (24 bits, [0, 1))
+ * widened to fp64; s = sqrt(r1), a = 1 - s, b = s (1 - r2), c = s r2; p = (a v0 + b v1) + c v2 per component, rounded
+ * to fp32 once.  A point depends on (key, i) alone: chunks [first, first + count) concatenate to the whole run.
+ * 0 <= first, 0 <= count (0: nothing is done), first + count <= LNR_CLOUD_MAX_POINTS: i fits the generator's 32-bit
+ * counter and the result fits the voxel filter. */
+int lnr_mesh_sample_points(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                           const int64_t* bounds, int64_t first, int64_t count, uint32_t key, float* points,
+                           int32_t* face_of, uint32_t* status, void* stream);
+/* normals (n_verts, 3) fp32: the sum of the cross products c (above: unnormalised, so area-weighted) of a vertex's
+ * incident faces divided by its norm sqrt((x x + y y) + z z), rounded to fp32; (0, 0, 1) for a zero sum.  The caller
+ * inverts the faces: corner_perm (3 n_faces int64) is the STABLE argsort of faces.reshape(-1), row_start (n_verts + 1
+ * int64) the exclusive scan of the vertices' corner counts.  One thread per vertex adds the c of face
+ * corner_perm[j] / 3 for j in [row_start[v], row_start[v + 1]), in that order: the order of every sum depends on the
+ * data alone.  Entries of corner_perm outside [0, 3 n_faces), rows outside it and faces with a bad index (which OR
+ * LNR_MESH_BAD_INDEX) are skipped, never followed.  A vertex runs as long as its row: marching-cubes meshes have
+ * valence 4 to about 12 and no list is split, so one vertex shared by a large part of the faces serialises them. */
+int lnr_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                            const int64_t* corner_perm, const int64_t* row_start, float* normals, uint32_t* status,
+                            void* stream);
 
 /* ---------------------------------------------------------------- utilities */
 /* dst[i] = lo + (hi-lo) * U(splitmix64(((uint64)seed << 32) + start + i)) */

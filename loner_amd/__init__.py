@@ -12,6 +12,8 @@ Host-side mirrors of the reference interface:
   step       FieldState / StepEngine: the fused optimiser step
   rays       world cube + LiDAR ray building    (src/common/ray_utils.py, pose_utils.py)
   meshing    Mesher: weight volume + marching cubes (analysis/mesher.py)
+  mesh_cloud a mesh as a uniformly sampled cloud, vertex normals, evaluate_mesh
+             (analysis/compute_metrics/maps/mesh_to_pcd.py, analysis/meshing.py)
   tracking   Tracker: cloud normals + two-stage point-to-plane ICP (src/tracking/tracker.py)
   synthetic  synthetic LiDAR scenes for the benchmark configs C1-C5
 """

@@ -9,7 +9,8 @@
     splat_max_ref, marching_cubes_ref
                              numpy restatements of the kernels' semantics with the same table and ordering: the
                              tests' CPU oracle, and what a host without a GPU can run
-    write_ply                binary little-endian PLY
+    write_ply, read_ply      binary little-endian PLY, with vertex normals on request (``mesh_cloud.vertex_normals``);
+                             the reader also takes Open3D's default output
 
 Volume layout: the accumulated volume is the reference's flat ``results``: cell = x_buck * nz + y_buck * nx * nz +
 z_buck, kept literally: the C-order index of an (ny, nx, nz) array; ``Mesher.volume()`` applies the reference's
@@ -118,19 +119,95 @@ def case_histogram(volume, level):
 
 
 # ---------------------------------------------------------------------------------------------- PLY
-def write_ply(path, vertices, faces):
-    """Binary little-endian PLY: float x, y, z per vertex; uchar 3 + int vertex_indices per face."""
+def write_ply(path, vertices, faces, normals=None):
+    """Binary little-endian PLY: float x, y, z (and nx, ny, nz when ``normals`` (V, 3) is given) per vertex; uchar 3 +
+    int vertex_indices per face."""
     v = np.ascontiguousarray(torch.as_tensor(vertices).detach().cpu().numpy(), "<f4").reshape(-1, 3)
     f = np.ascontiguousarray(torch.as_tensor(faces).detach().cpu().numpy(), "<i4").reshape(-1, 3)
+    names = "xyz"
+    if normals is not None:
+        n = np.ascontiguousarray(torch.as_tensor(normals).detach().cpu().numpy(), "<f4").reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError(f"write_ply: {len(n)} normals for {len(v)} vertices")
+        v, names = np.ascontiguousarray(np.concatenate((v, n), axis=1)), ("x", "y", "z", "nx", "ny", "nz")
     rec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
     rec["n"], rec["i"] = 3, f
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {len(v)}\n" + "".join(f"property float {a}\n" for a in names) +
               f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as fh:
         fh.write(header.encode("ascii"))
         fh.write(v.tobytes())
         fh.write(rec.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4",
+              "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path):
+    """(vertices (V, 3) float32, faces (F, 3) int32, normals (V, 3) float32 or None) of a triangle-mesh PLY: what
+    ``write_ply`` writes and Open3D's default output.  Format binary_little_endian or ascii; element vertex with
+    float or double x y z, optional nx ny nz of either type and any further scalar properties (colours), which are
+    skipped; element face with one ``list uchar int|uint vertex_indices`` of 3 per face.  Anything else raises
+    ValueError naming the header line."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    end = raw.find(b"end_header")
+    stop = raw.find(b"\n", end) if end >= 0 else -1
+    if not raw.startswith(b"ply") or stop < 0:
+        raise ValueError(f"read_ply: {path}: no PLY header")
+    fmt, elements = None, []
+    for line in raw[:stop].decode("ascii", "replace").splitlines()[1:]:
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info", "end_header"):
+            continue
+        bad = ValueError(f"read_ply: unsupported header line {line.strip()!r}")
+        if w[0] == "format" and len(w) == 3 and w[1] in ("binary_little_endian", "ascii") and w[2] == "1.0":
+            fmt = w[1]
+        elif w[0] == "element" and len(w) == 3 and w[1] in ("vertex", "face") and w[2].isdigit() and \
+                w[1] not in [e[0] for e in elements]:
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property" and elements and elements[-1][0] == "vertex" and len(w) == 3 and w[1] in _PLY_TYPES:
+            if w[2] in ("x", "y", "z", "nx", "ny", "nz") and w[1] not in ("float", "float32", "double", "float64"):
+                raise bad
+            elements[-1][2].append((w[2], "<" + _PLY_TYPES[w[1]]))
+        elif w[0] == "property" and elements and elements[-1][0] == "face" and len(w) == 5 and w[1] == "list" and \
+                w[2] in ("uchar", "uint8") and w[3] in ("int", "int32", "uint", "uint32") and \
+                w[4] in ("vertex_indices", "vertex_index") and not elements[-1][2]:
+            elements[-1][2].append(("i", "<" + _PLY_TYPES[w[3]]))
+        else:
+            raise bad
+    if fmt is None or [e[0] for e in elements] != ["vertex", "face"] or not elements[1][2]:
+        raise ValueError(f"read_ply: {path}: the header needs a format line, then element vertex, then element face "
+                         "with its vertex_indices")
+    (_, nv, vprops), (_, nf, fprops) = elements
+    names = [p[0] for p in vprops]
+    if len(set(names)) != len(names) or not all(a in names for a in "xyz"):
+        raise ValueError(f"read_ply: {path}: element vertex needs x, y, z once each, got {names}")
+    has_normals = all(a in names for a in ("nx", "ny", "nz"))
+    body = raw[stop + 1:]
+    if fmt == "ascii":
+        tok = body.split()
+        if len(tok) < nv * len(names) + nf * 4:
+            raise ValueError(f"read_ply: {path}: the data ends early")
+        vt = np.array(tok[:nv * len(names)], dtype=np.float64).reshape(nv, len(names))
+        col = {a: vt[:, k] for k, a in enumerate(names)}
+        ft = np.array(tok[nv * len(names):nv * len(names) + nf * 4], dtype=np.int64).reshape(nf, 4)
+        counts, idx = ft[:, 0], ft[:, 1:]
+    else:
+        vdt, fdt = np.dtype(vprops), np.dtype([("n", "u1"), ("i", fprops[0][1], (3,))])
+        if len(body) < nv * vdt.itemsize + nf * fdt.itemsize:
+            raise ValueError(f"read_ply: {path}: the data ends early")
+        col = np.frombuffer(body, vdt, nv)
+        frec = np.frombuffer(body, fdt, nf, nv * vdt.itemsize)
+        counts, idx = frec["n"], frec["i"]
+    if (counts != 3).any():
+        raise ValueError(f"read_ply: {path}: a face is not a triangle")
+    vertices = np.stack([col[a] for a in "xyz"], axis=1).astype(np.float32)
+    normals = np.stack([col[a] for a in ("nx", "ny", "nz")], axis=1).astype(np.float32) if has_normals else None
+    return vertices, np.ascontiguousarray(idx).astype(np.int32), normals
 
 
 # ---------------------------------------------------------------------------------------------- directions
