@@ -628,7 +628,7 @@ __device__ __forceinline__ float rec_v1(uint32_t h) { return (float)__builtin_bi
 
 struct BwdWorkspace {
   uint32_t* hist;        // per level l: [n_sb][nb_l] record counts -> exclusive offsets within bucket
-  uint32_t* chunk_sum;   // [L][n_chunks][kMaxChunksPerLevel] per-chunk column sums (k_bwd_chunk_sums)
+  uint32_t* chunk_sum;   // [L][n_chunks][kMaxChunksPerLevel] per-chunk column sums (k_bwd_chunk_sums; live: k_bwd_count_live)
   float* level_max;      // [LNR_MAX_LEVELS] max |d_enc| per level (as uint bits: k_denc_level_max's atomicMax)
   uint32_t* counts;      // [kMaxBuckets] records per bucket (the scatter's: placement, work split)
   uint64_t* seg_start;   // [kMaxBuckets + 1]
@@ -638,7 +638,7 @@ struct BwdWorkspace {
   uint2* rec;            // [8 * N * L] records {word, half2} (see "Backward records")
   // the live backward (LNR_BWD_LIVE): its histogram rows are groups of 8 live waves (64-sample groups holding a
   // sample with dL/dsigma != 0), listed in sample order
-  uint8_t* wflags;       // [ceil(N / 64)] wave w holds a live sample
+  uint64_t* wmask;       // [ceil(N / 4096)] bit w of word s: wave 64 s + w holds a live sample (k_bwd_live_masks)
   uint32_t* wlist;       // [ceil(N / 64)] the live waves, ascending
   uint32_t* live;        // [2] live waves, live rows (= ceil(live waves / 8))
   int64_t n_sb;
@@ -653,7 +653,7 @@ inline int64_t bwd_n_chunks(int64_t n) { return (bwd_n_sb(n) + kRowsPerChunk - 1
 inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
 struct WsLayout {
-  int64_t hist, chunk_sum, level_max, counts, seg_start, partial, bucket_done, units, wflags, wlist, live, rec,
+  int64_t hist, chunk_sum, level_max, counts, seg_start, partial, bucket_done, units, wmask, wlist, live, rec,
       total;
 };
 
@@ -669,7 +669,7 @@ inline WsLayout ws_layout(const lnr_grid_desc* d, const GridArgs& a, int64_t n) 
   w.partial = b;   b += align256((int64_t)2 * kAccumGroups * 2 * kChunk * 8);
   w.bucket_done = b; b += align256(kMaxBuckets * 4);
   w.units = b;     b += align256(sizeof(UnitTable));
-  w.wflags = b;    b += align256((n + 63) / 64);
+  w.wmask = b;     b += align256(((n + 4095) / 4096 + 1) * 8);
   w.wlist = b;     b += align256((n + 63) / 64 * 4);
   w.live = b;      b += align256(2 * 4);
   // +2 records: the accumulate loads records in pairs
@@ -702,7 +702,7 @@ inline BwdWorkspace carve_workspace(void* base, const GridArgs& a, const lnr_gri
   w.partial = reinterpret_cast<long long*>(p + L.partial);
   w.bucket_done = reinterpret_cast<uint32_t*>(p + L.bucket_done);
   w.units = reinterpret_cast<UnitTable*>(p + L.units);
-  w.wflags = reinterpret_cast<uint8_t*>(p + L.wflags);
+  w.wmask = reinterpret_cast<uint64_t*>(p + L.wmask);
   w.wlist = reinterpret_cast<uint32_t*>(p + L.wlist);
   w.live = reinterpret_cast<uint32_t*>(p + L.live);
   w.rec = reinterpret_cast<uint2*>(p + L.rec);

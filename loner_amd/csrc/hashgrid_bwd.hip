@@ -6,7 +6,8 @@
 //   count    per (512-sample row, level) record histogram over the level's 4096-entry table chunks
 //            (buckets), emitted by the training forward (k_hashgrid_fwd given the workspace) or by k_bwd_count
 //   scan     k_bwd_chunk_sums + k_bwd_scan_rows (column prefix over 64-row chunks) + k_bwd_scan_buckets:
-//            exact per-row record offsets in every bucket (no global atomics, no capacity guess)
+//            exact per-row record offsets in every bucket (no capacity guess; the live backward's count adds
+//            its rows into the chunk sums itself, integer atomics: no k_bwd_chunk_sums launch)
 //   scatter  k_bwd_scatter_rows: one workgroup per row walks all 16 levels; 8-byte records {word,
 //            fp16 value pair at the level's power-of-two scale} (hashgrid.hpp "Backward records": one
 //            per x-pair of corners at fine levels, one per corner of a run of lanes in one cell at the
@@ -237,63 +238,59 @@ __device__ __forceinline__ bool run_live(unsigned long long wl, const RunInfo& r
   return (wl & upto & ~((1ull << ri.head_lane) - 1ull)) != 0ull;
 }
 
-// The live waves: wflags[w] = some sample of the 64-sample group w has dL/dsigma != 0 (16 threads of 4 samples
-// per group), then k_bwd_live_list lists them in order and counts them (ws.live: waves, rows of 8).
-__global__ void __launch_bounds__(256) k_bwd_live_flags(const float* __restrict__ dsig, int64_t n, BwdWorkspace ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t i = 4 * t;
-  bool lv = false;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) lv = lv || (i + k < n && dsig[i + k] != 0.f);
-  const unsigned long long b = __ballot(lv);
-  const int lane = threadIdx.x & 63;
-  if ((lane & 15) == 0 && i < n) ws.wflags[t >> 4] = ((b >> lane) & 0xFFFFull) != 0ull ? 1 : 0;
-}
-// One workgroup: passes of 1024 x 64 wave flags, each thread listing the live ones among its 64 in order.
-__global__ void __launch_bounds__(1024) k_bwd_live_list(int64_t n_waves, BwdWorkspace ws) {
-  __shared__ uint32_t wsum[16];
-  __shared__ uint32_t carry;
+// The live waves, in two launches of small workgroups (a wave per SIMD, a handful of registers: they fit in the 64
+// registers per SIMD the MLP backward's one round of workgroups leaves free beside it), the list spread over a wave
+// per slab instead of one workgroup's passes (the list ends 5 us earlier at C2).
+//   k_bwd_live_masks  one workgroup per slab of kLiveSlab 64-sample groups (waves): wmask[slab] bit w = some
+//                     sample of the slab's wave w has dL/dsigma != 0 (16 lanes of 4 samples per wave and load)
+//   k_bwd_live_list   one wave per slab: its offset = the live waves of the slabs before it (their masks'
+//                     popcounts, summed anew by every slab: at most n / 4096 eight-byte L2 reads), then its live
+//                     waves into ws.wlist, ascending; the last slab writes ws.live (waves, rows of 8)
+// No workgroup waits for another and nothing is counted in memory: the workspace needs no initial state.
+// k_bwd_live_masks also zeroes the chunk sums k_bwd_count_live adds into.
+constexpr int kLiveSlab = 64;  // waves per slab: one 64-bit mask
+template <bool VEC>  // VEC: dsig is 16-byte aligned
+__global__ void __launch_bounds__(256) k_bwd_live_masks(const float* __restrict__ dsig, int64_t n, BwdWorkspace ws,
+                                                        int64_t n_chunk_sums) {
+  __shared__ unsigned long long part[4];
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-  if (t == 0) carry = 0u;
-  for (int64_t p0 = 0; p0 < n_waves; p0 += 1024 * 64) {
-    const int64_t f0 = p0 + 64 * (int64_t)t;
-    unsigned long long m = 0ull;
-    if (f0 + 64 <= n_waves) {  // 64 flags in four 16-B loads (the flags array is 256-B aligned)
-      uint4 q[4];
+  const int64_t s0 = (int64_t)blockIdx.x * (kLiveSlab * 64);
+  unsigned long long m = 0ull;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) q[k] = reinterpret_cast<const uint4*>(ws.wflags + f0)[k];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const uint32_t wd = k % 4 == 0 ? q[k / 4].x : k % 4 == 1 ? q[k / 4].y : k % 4 == 2 ? q[k / 4].z : q[k / 4].w;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) m |= ((wd >> (8 * b)) & 0xFFu) ? 1ull << (4 * k + b) : 0ull;
-      }
+  for (int k = 0; k < kLiveSlab / 16; ++k) {  // 256 threads x 4 samples = 16 waves per load
+    const int64_t i = s0 + 4 * (int64_t)(k * 256 + t);
+    bool lv = false;
+    if (VEC && i + 4 <= n) {
+      const float4 q = *reinterpret_cast<const float4*>(dsig + i);
+      lv = q.x != 0.f || q.y != 0.f || q.z != 0.f || q.w != 0.f;
     } else {
-      for (int k = 0; k < 64; ++k)
-        if (f0 + k < n_waves && ws.wflags[f0 + k]) m |= 1ull << k;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lv = lv || (i + j < n && dsig[i + j] != 0.f);
     }
-    const uint32_t c = (uint32_t)__popcll(m);
-    const uint32_t inc = wave_incl_scan_u32(c);
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    uint32_t off = carry, tot = carry;
-    for (int w = 0; w < 16; ++w) {
-      if (w < wid) off += wsum[w];
-      tot += wsum[w];
-    }
-    off += inc - c;
-    while (m) {
-      const int k = __builtin_ctzll(m);
-      m &= m - 1ull;
-      ws.wlist[off++] = (uint32_t)(f0 + k);
-    }
-    __syncthreads();
-    if (t == 0) carry = tot;
-    __syncthreads();
+    const unsigned long long b = __ballot(lv);
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      if ((b >> (16 * g)) & 0xFFFFull) m |= 1ull << (16 * k + 4 * wid + g);
   }
-  if (t == 0) {
-    ws.live[0] = carry;
-    ws.live[1] = (carry + 7u) / 8u;
+  if (lane == 0) part[wid] = m;
+  __syncthreads();
+  if (t == 0) ws.wmask[blockIdx.x] = part[0] | part[1] | part[2] | part[3];
+  for (int64_t j = (int64_t)blockIdx.x * 256 + t; j < n_chunk_sums; j += (int64_t)gridDim.x * 256) ws.chunk_sum[j] = 0u;
+}
+__global__ void __launch_bounds__(64) k_bwd_live_list(int64_t n_slabs, BwdWorkspace ws) {
+  const int lane = threadIdx.x;
+  const int64_t sl = blockIdx.x;
+  uint32_t off = 0;
+  for (int64_t j = lane; j < sl; j += 64) off += (uint32_t)__popcll(ws.wmask[j]);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) off += __shfl_xor(off, o, 64);
+  const unsigned long long m = ws.wmask[sl];
+  if ((m >> lane) & 1ull)
+    ws.wlist[off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)(sl * kLiveSlab + lane);
+  if (sl == n_slabs - 1 && lane == 0) {
+    const uint32_t tot = off + (uint32_t)__popcll(m);
+    ws.live[0] = tot;
+    ws.live[1] = (tot + 7u) / 8u;
   }
 }
 
@@ -340,11 +337,23 @@ __global__ void __launch_bounds__(kSB) k_bwd_count_live(GridArgs a, PosFn pos, i
     }
   }
   lds_barrier();
+  // the row, and its share of its scan chunk's column sums (k_bwd_live_masks zeroed them; integer adds: any order
+  // gives the same sums); wave w publishes levels 2w and 2w + 1
+  static_assert(NL <= 2 * (kSB / 64), "wave w publishes levels 2w and 2w + 1");
+  const bool sums = ws.n_chunks > 1;  // (one chunk: k_bwd_scan_rows sums the rows itself)
 #pragma unroll
-  for (int l = 0; l < NL; ++l) {
-    const uint32_t nb = a.bucket_base[l + 1] - a.bucket_base[l];
-    uint32_t* row = hist_row(a, ws, l, sb);
-    for (uint32_t b = threadIdx.x; b < nb; b += kSB) row[b] = hist[l * NB + b];
+  for (int p = 0; p < 2; ++p) {
+    const int l = 2 * wid + p;
+    if (l < NL) {
+      const uint32_t nb = a.bucket_base[l + 1] - a.bucket_base[l];
+      uint32_t* row = hist_row(a, ws, l, sb);
+      uint32_t* cs = ws.chunk_sum + ((int64_t)l * ws.n_chunks + sb / kRowsPerChunk) * kMaxChunksPerLevel;
+      for (uint32_t b = lane; b < nb; b += 64) {
+        const uint32_t v = hist[l * NB + b];
+        row[b] = v;
+        if (sums && v) __hip_atomic_fetch_add(cs + b, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
   }
 }
 
@@ -1543,20 +1552,19 @@ static int launch_bwd_bucketed(const lnr_grid_desc* d, PosFn pos, int64_t n, Gra
                          w);
     if (live) {
       if constexpr (GradFn::kScaled) {
-        const int64_t n_waves = (n + 63) / 64;
-        hipLaunchKernelGGL(k_bwd_live_flags, dim3((unsigned)((n_waves * 16 + 255) / 256)), dim3(256), 0, st, grad.dsig, n,
-                           w);
-        hipLaunchKernelGGL(k_bwd_live_list, dim3(1), dim3(1024), 0, st, n_waves, w);
+        const int64_t n_waves = (n + 63) / 64, n_slabs = std::max<int64_t>((n_waves + kLiveSlab - 1) / kLiveSlab, 1);
+        const int64_t n_cs = w.n_chunks > 1 ? (int64_t)d->n_levels * w.n_chunks * kMaxChunksPerLevel : 0;
+        hipLaunchKernelGGL(((reinterpret_cast<uintptr_t>(grad.dsig) & 15u) == 0 ? k_bwd_live_masks<true>
+                                                                                  : k_bwd_live_masks<false>),
+                           dim3((unsigned)n_slabs), dim3(256), 0, st, grad.dsig, n, w, n_cs);
+        hipLaunchKernelGGL(k_bwd_live_list, dim3((unsigned)n_slabs), dim3(64), 0, st, n_slabs, w);
         auto cnt = m == 3   ? k_bwd_count_live<PosFn, 16, 3, 64>
                    : m == 4 ? k_bwd_count_live<PosFn, 16, 4, 64>
                    : m == 5 ? k_bwd_count_live<PosFn, 16, 5, 64>
                    : m == 6 ? k_bwd_count_live<PosFn, 16, 6, 64>
                             : k_bwd_count_live<PosFn, 16, 7, 64>;
         hipLaunchKernelGGL(cnt, dim3((unsigned)w.n_sb), dim3(kSB), 0, st, a, pos, n, grad.dsig, w);
-        w.use_live = true;  // the scans and the scatter below: the live rows
-        if (w.n_chunks > 1)
-          hipLaunchKernelGGL(k_bwd_chunk_sums, dim3((unsigned)w.n_chunks, d->n_levels), dim3(kMaxChunksPerLevel), 0, st, a,
-                             w);
+        w.use_live = true;  // the scans and the scatter below: the live rows (the count summed their chunks' columns)
       }
     }
     hipLaunchKernelGGL(k_bwd_scan_rows, dim3((unsigned)w.n_chunks, d->n_levels), dim3(kMaxChunksPerLevel), 0, st, a, w);
@@ -1575,7 +1583,9 @@ static int launch_bwd_bucketed(const lnr_grid_desc* d, PosFn pos, int64_t n, Gra
                   : m == 5 ? k_bwd_scatter_rows<PosFn, GradFn, 16, 5, 64, true>
                   : m == 6 ? k_bwd_scatter_rows<PosFn, GradFn, 16, 6, 64, true>
                            : k_bwd_scatter_rows<PosFn, GradFn, 16, 7, 64, true>;
-      hipLaunchKernelGGL(kern, dim3((unsigned)w.n_sb), dim3(kSB), 0, st, a, pos, n, grad, w, skip_zero);
+      // (whole groups of 8 workgroups: the kernel deals its live rows, rounded up to 8, over the XCDs; with fewer
+      // workgroups than that, the last rows of XCDs 1-7 had none when nearly every row of an odd row count was live)
+      hipLaunchKernelGGL(kern, dim3((unsigned)((w.n_sb + 7) / 8 * 8)), dim3(kSB), 0, st, a, pos, n, grad, w, skip_zero);
     }
   } else if (rows64) {
     auto kern = m == 3   ? k_bwd_scatter_rows<PosFn, GradFn, 16, 3, 64>

@@ -22,7 +22,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BWD_KERNELS = ("k_bwd_col_totals", "k_bwd_live_flags", "k_bwd_live_list", "k_bwd_count_live", "k_bwd_chunk_sums",
+BWD_KERNELS = ("k_bwd_col_totals", "k_bwd_live_flags", "k_bwd_live_masks", "k_bwd_live_list", "k_bwd_count_live", "k_bwd_chunk_sums",
                "k_bwd_scan_rows", "k_bwd_scan_buckets", "k_bwd_scatter_rows", "k_bwd_scatter", "k_denc_level_max",
                "k_bwd_accum", "k_bwd_finalize", "k_bwd_accum_units", "k_bwd_finalize_units", "k_bwd_accum_buckets",
                "k_bwd_units")
