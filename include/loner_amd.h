@@ -763,7 +763,50 @@ int64_t lnr_dist_stats_workspace_bytes(int64_t n);
 int lnr_dist_stats(const double* dist, int64_t n, double threshold, void* workspace, int64_t ws_bytes, double* out,
                    void* stream);
 
-/* ---------------------------------------------------------------- mesh sampling (analysis/compute_metrics/maps/mesh_to_pcd.py) */
+/* ---------------------------------------------------------------- ground-truth LiDAR map (examples/fusion_portable/create_lidar_map.py) */
+/* A return at its own pose, k nearest neighbours on the grid of lnr_nn_search, and the two sums of Open3D's
+ * remove_statistical_outlier.  status: 1 device uint32, ORed into and never cleared here.  No float atomics; every
+ * result repeats bit for bit. */
+#define LNR_KNN_MAX_K 64                    /* neighbours per query: one per lane of a wave */
+/* out[p] (n, 3) fp32 = fp32(R pts[p] + x), the pose (R, x) of the trajectory at t[p] (fp64, absolute seconds), all in
+ * fp64 and rounded once.  The trajectory: traj_t (n_poses, strictly increasing), traj_xyz (n_poses, 3), traj_rot
+ * (n_poses, 9, row-major), rel_rotvec (n_poses - 1, 3) = the rotation vector of R_i^-1 R_i+1; DEVICE float64, prepared
+ * on the host (loner_amd/lidar_map.py).  Interval i = searchsorted(traj_t, t, 'left') - 1, a t equal to traj_t[0] in
+ * interval 0 (scipy's Slerp and interp1d); alpha = (t - t_i) / (t_i+1 - t_i); R = R_i exp(alpha rel_rotvec_i)
+ * (Rodrigues, the series 1 - th^2 / 6 and 1 / 2 - th^2 / 24 below 1e-4 rad); x = x_i + alpha (x_i+1 - x_i).
+ * valid[p] (uint8) = 0 and out[p] = 0 when |pts[p]| (fp64) is not > min_range, when t[p] lies outside
+ * [traj_t[0], traj_t[n_poses - 1]] (never extrapolated), or when an input or the result is nan or inf, which also
+ * ORs LNR_CLOUD_NONFINITE into *status.  1 <= n <= LNR_CLOUD_MAX_POINTS, 2 <= n_poses. */
+int lnr_trajectory_transform(const float* pts, const double* t, int64_t n, const double* traj_t,
+                             const double* traj_xyz, const double* traj_rot, const double* rel_rotvec,
+                             int64_t n_poses, double min_range, float* out, uint8_t* valid, uint32_t* status,
+                             void* stream);
+/* The exact k nearest targets of each point of src (n_src, 3) by the key of lnr_nn_search, (d2, index) with d2 in fp32
+ * and every operation rounded; the target is described as there (tgt_sorted, tgt_keys, tgt_perm, origin, cell, dims).
+ * idx (n_src, k) int32 in the caller's indices and d2 (n_src, k) fp32, both ascending by the key; mean_dist (n_src)
+ * fp64 when not NULL: the fp64 distances to the k winners (recomputed from the coordinates), added in list order,
+ * divided by k.  A query that is a target finds itself at distance 0.  One wave per query expands Chebyshev rings and
+ * stops after ring r >= 1 once it holds k keys and the k-th d2 <= (r cell)^2 (1 - 2^-20), or when the box is covered;
+ * after LNR_NN_MAX_RINGS rings, or at a ring of more than 81 columns, it joins a list in the workspace (an integer
+ * counter; no result depends on the list's order) and is answered by an exhaustive scan with the same key: the result
+ * is the exact k smallest keys over all targets, whatever `cell` is.  A non-finite query ORs LNR_CLOUD_NONFINITE into
+ * *status and its row is idx -1, d2 = mean_dist = inf; so are the entries a query cannot fill because fewer than k
+ * targets are finite.  1 <= k <= min(LNR_KNN_MAX_K, n_tgt); sizes and cell as for lnr_nn_search.  workspace:
+ * lnr_knn_workspace_bytes(n_src) bytes (0 for an n_src outside the limits), 8-byte aligned. */
+int64_t lnr_knn_workspace_bytes(int64_t n_src);
+int lnr_knn_search(const float* src, int64_t n_src, const float* tgt_sorted, const int64_t* tgt_keys,
+                   const int32_t* tgt_perm, int64_t n_tgt, const double* origin, double cell, const int32_t* dims,
+                   int32_t k, void* workspace, int64_t ws_bytes, int32_t* idx, float* d2, double* mean_dist,
+                   uint32_t* status, void* stream);
+/* Over the entries v[i] > 0 of v (n fp64): out[0] = their sum, out[1] = their number (as a double), out[2] = the sum
+ * of (v[i] - c)^2, c = *centre_dev when centre_dev (1 DEVICE double) is not NULL, else `centre`.  One row of partial
+ * sums per 4096 entries in the workspace, the rows added in a fixed order.  The workspace query returns 0 for n
+ * outside [1, LNR_CLOUD_MAX_POINTS]. */
+int64_t lnr_dist_moments_workspace_bytes(int64_t n);
+int lnr_dist_moments(const double* v, int64_t n, double centre, const double* centre_dev, void* workspace,
+                     int64_t ws_bytes, double* out, void* stream);
+
+/* ---------------------------------------------------------------- mesh sampling(analysis/compute_metrics/maps/mesh_to_pcd.py) */
 /* A triangle mesh as a cloud (Open3D's sample_points_uniformly) and its vertex normals (compute_vertex_normals,
  * analysis/meshing.py:122).  verts (n_verts, 3) fp32, faces (n_faces, 3) int32; 1 <= n_verts < 2^31,
  * 1 <= n_faces <= LNR_CLOUD_MAX_POINTS.  status: 1 device uint32, ORed into and never cleared here.  A face with an

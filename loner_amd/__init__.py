@@ -14,6 +14,9 @@ Host-side mirrors of the reference interface:
   meshing    Mesher: weight volume + marching cubes (analysis/mesher.py)
   mesh_cloud a mesh as a uniformly sampled cloud, vertex normals, evaluate_mesh
              (analysis/compute_metrics/maps/mesh_to_pcd.py, analysis/meshing.py)
+  map_eval   rendered cloud, voxel filter, Chamfer / F-score (analysis/evaluate_lidar_map.py, renderer_lidar.py)
+  lidar_map  ground-truth map: per-return trajectory deskew, grid kNN, statistical outlier filter, masking
+             (examples/fusion_portable/create_lidar_map.py, mask_gt_with_trajectory.py)
   tracking   Tracker: cloud normals + two-stage point-to-plane ICP (src/tracking/tracker.py)
   synthetic  synthetic LiDAR scenes for the benchmark configs C1-C5
 """

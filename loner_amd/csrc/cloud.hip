@@ -19,33 +19,19 @@
 //                     block adds the rows.
 // Integer atomics only (the status word); every floating-point sum has a shape fixed by the sizes and the data:
 // results repeat bit for bit.
-#include "common.hpp"
+#include "cloud_grid.hpp"
 
 namespace lnr {
 
 constexpr int kCloudBlock = 256;
 constexpr int kVoxChunk = LNR_CLOUD_VOXEL_CHUNK;
-constexpr int kCellBits = LNR_CLOUD_CELL_BITS;
 constexpr double kCellLimit = (double)(1 << kCellBits);
-constexpr int64_t kBadKey = LNR_CLOUD_BAD_KEY;
-constexpr int kNnMaxRings = LNR_NN_MAX_RINGS;
-constexpr int kNnMaxColumns = 81;                    // a ring cut to the box may not hold more columns than ring 4
-constexpr double kNnMargin = 9.5367431640625e-07;    // 2^-20, see k_nn_grid
-constexpr uint64_t kNoNnKey = ~(uint64_t)0;
 constexpr int kNnBrutePts = 4;                       // queries per wave and pass of the exhaustive scan
 constexpr int kNnTile = 1024;                        // target points per LDS tile (12 KiB)
 constexpr int kNnPerPass = kNnBrutePts * (kCloudBlock / kWave);  // queries per block and pass
 constexpr int kNnBruteBlocks = 1024;                 // at most: four per CU
 constexpr int kStatPer = 16;                         // entries per thread of a partial row
 constexpr int kStatTile = kCloudBlock * kStatPer;    // 4096 entries per row
-
-__device__ __forceinline__ int64_t cell_key(int64_t ix, int64_t iy, int64_t iz) {
-  return (ix << (2 * kCellBits)) | (iy << kCellBits) | iz;
-}
-// floor((double(p) - origin) / cell): one IEEE subtraction, one IEEE division (no reciprocal), as numpy computes it
-__device__ __forceinline__ double cell_coord(float p, double origin, double cell) {
-  return floor(__ddiv_rn(__dsub_rn((double)p, origin), cell));
-}
 
 // ------------------------------------------------------------------ keys
 __global__ void __launch_bounds__(kCloudBlock)
@@ -144,26 +130,6 @@ __global__ void __launch_bounds__(kCloudBlock)
 }
 
 // ------------------------------------------------------------------ nearest neighbour
-// (d^2, index) as one integer: non-negative floats order like their bit patterns, ties go to the lower index.
-__device__ __forceinline__ uint64_t nn_pair(float d2, uint32_t idx) {
-  return ((uint64_t)__float_as_uint(d2) << 32) | idx;
-}
-// Every operation rounded on its own, in this order: contraction can never change the bits.
-__device__ __forceinline__ float nn_dist2(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-// The first position in [lo, hi) whose key is >= k (hi if none).
-__device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ keys, int64_t lo, int64_t hi, int64_t k) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 struct NnBest {
   uint64_t pair;  // nn_pair of the best so far
   int64_t pos;    // its sorted position
