@@ -806,6 +806,42 @@ int64_t lnr_dist_moments_workspace_bytes(int64_t n);
 int lnr_dist_moments(const double* v, int64_t n, double centre, const double* centre_dev, void* workspace,
                      int64_t ws_bytes, double* out, void* stream);
 
+/* ---------------------------------------------------------------- registration on the cell grid (full-size clouds) */
+/* lnr_cloud_normals and lnr_icp_stage for clouds their exhaustive searches cannot take: the neighbours come from the
+ * grid of lnr_nn_search.  Both searches order targets by the same (fp32 d2, index) key and both paths add the same
+ * fp64 terms in the same order, so wherever both can run the results are the same bits. */
+/* normals[i] (n, 3) fp32 of the query pts[i] (n, 3) from its neighbour list: the points tgt[idx[i * k + j]], j < k, in
+ * the order given (idx (n, k) int32, lnr_knn_search's).  The same steps as lnr_cloud_normals after its search: fp64
+ * mean and covariance, the eigenvector of the smallest eigenvalue, (0, 0, 1) for a zero covariance, turned so that
+ * normal . pts[i] <= 0; with the list lnr_cloud_normals finds, the same bits.  A row with an index outside
+ * [0, n_tgt) follows none of its indices and gets the fallback (0, 0, 1), turned the same way.  3 <= k <= 64,
+ * 1 <= n, n_tgt <= LNR_CLOUD_MAX_POINTS. */
+int lnr_normals_from_knn(const float* pts, int64_t n, const float* tgt, int64_t n_tgt, const int32_t* idx, int32_t k,
+                         float* normals, void* stream);
+/* Host only: the rings of `cell` a correspondence search with `threshold` has to walk, the smallest R >= 1 with
+ * (R cell)^2 (1 - 2^-20) >= thr2, thr2 = (float)((double)threshold * threshold) as lnr_icp_stage forms it: a target
+ * outside rings 0 .. R has a key strictly above that bound (lnr_nn_search's stopping rule) and cannot be a kept pair.
+ * 0 when R would exceed LNR_NN_MAX_RINGS, or for a threshold that is not positive and finite (its fp32 square
+ * included) or a cell outside [1e-12, inf). */
+int32_t lnr_icp_grid_rings(float threshold, double cell);
+int64_t lnr_icp_grid_workspace_bytes(int64_t n_src);  /* 0 for an n_src outside [1, LNR_ICP_MAX_POINTS] */
+/* lnr_icp_stage with the target as a grid (tgt_sorted, tgt_keys, tgt_perm, origin, cell, dims as for lnr_nn_search;
+ * tgt_normals (n_tgt, 3) in the caller's order, which corr_idx also reports).  The contract is lnr_icp_stage's:
+ * max_iterations + 1 rounds enqueued by this call, rounds after convergence do nothing, the first round clears
+ * `converged` and `iterations` and keeps T, so grid and exhaustive stages chain on one state; partial rows of 16
+ * consecutive source points, each added in index order, and the same update: the state after every round, corr_idx
+ * and corr_d2 are lnr_icp_stage's bit for bit.  A query walks the rings of its cell as in lnr_nn_search but never
+ * beyond R = lnr_icp_grid_rings(threshold, cell), and there is no exhaustive pass: a query without a target in rings
+ * 0 .. R has no pair, as d2 < thr2 would have decided.  The call is refused before any launch when R is 0.  A source
+ * point whose p = T s is not finite has no pair and ORs LNR_CLOUD_NONFINITE into *status (1 device uint32, never
+ * cleared here); a target with LNR_CLOUD_BAD_KEY sorts last and is never visited.  workspace:
+ * lnr_icp_grid_workspace_bytes(n_src) bytes, 8-byte aligned. */
+int lnr_icp_stage_grid(const float* src, int64_t n_src, const float* tgt_sorted, const int64_t* tgt_keys,
+                       const int32_t* tgt_perm, int64_t n_tgt, const double* origin, double cell, const int32_t* dims,
+                       const float* tgt_normals, float threshold, int32_t max_iterations, double rel_fitness,
+                       double rel_rmse, lnr_icp_state* state, void* workspace, int64_t ws_bytes, int32_t* corr_idx,
+                       float* corr_d2, uint32_t* status, void* stream);
+
 /* ---------------------------------------------------------------- mesh sampling(analysis/compute_metrics/maps/mesh_to_pcd.py) */
 /* A triangle mesh as a cloud (Open3D's sample_points_uniformly) and its vertex normals (compute_vertex_normals,
  * analysis/meshing.py:122).  verts (n_verts, 3) fp32, faces (n_faces, 3) int32; 1 <= n_verts < 2^31,

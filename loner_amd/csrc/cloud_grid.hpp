@@ -40,4 +40,29 @@ __device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ keys,
   return lo;
 }
 
+// ------------------------------------------------------------------ one query's walk (k_nn_grid, k_icp_correspond_grid)
+struct NnBest {
+  uint64_t pair;  // nn_pair of the best so far
+  int64_t pos;    // its sorted position
+};
+
+// One candidate: the index is only read when the distance does not lose outright.
+__device__ __forceinline__ void nn_offer(float d2, int64_t j, const int32_t* __restrict__ tperm, NnBest& b) {
+  if (__float_as_uint(d2) > (uint32_t)(b.pair >> 32)) return;  // d2 >= 0: bit order is value order
+  const uint64_t pair = nn_pair(d2, (uint32_t)tperm[j]);
+  if (pair < b.pair) b.pair = pair, b.pos = j;
+}
+
+// Cells z0 .. z1 of column (x, y): contiguous in key order.  [lo, hi) are the sorted positions of the column's row
+// (x fixed, the ring's y range), so the search is short and stays in a few cache lines.  Only positions below hi <=
+// n_tgt are read; a key is compared, never followed.
+__device__ __forceinline__ void nn_scan_run(const float* __restrict__ tp, const int64_t* __restrict__ tk,
+                                            const int32_t* __restrict__ tperm, int64_t lo, int64_t hi, int64_t x,
+                                            int64_t y, int64_t z0, int64_t z1, float qx, float qy, float qz,
+                                            NnBest& b) {
+  const int64_t khi = cell_key(x, y, z1);
+  for (int64_t j = lower_bound(tk, lo, hi, cell_key(x, y, z0)); j < hi && tk[j] <= khi; ++j)
+    nn_offer(nn_dist2(qx, qy, qz, tp[j * 3], tp[j * 3 + 1], tp[j * 3 + 2]), j, tperm, b);
+}
+
 }  // namespace lnr

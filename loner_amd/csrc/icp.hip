@@ -12,7 +12,7 @@
 // A stage is max_iterations + 1 rounds of (correspond, update) enqueued at once; every kernel of a round after the
 // first returns at once when state->converged is set, so the stream needs no host decision.
 // Every sum has a fixed shape (lane butterflies, then rows in index order): results repeat bit for bit.
-#include "common.hpp"
+#include "icp_math.hpp"
 
 namespace lnr {
 
@@ -20,9 +20,7 @@ constexpr int kIcpBlock = 256;                        // 4 waves
 constexpr int kIcpWaves = kIcpBlock / kWave;
 constexpr int kIcpTile = 1024;                        // points of the searched cloud per LDS tile (12 KiB)
 constexpr int kIcpPts = 4;                            // source points per wave
-constexpr int kIcpBlockPts = kIcpPts * kIcpWaves;     // 16 source points per block
-constexpr int kIcpRow = 32;                           // doubles per partial row: 27 sums, count, sum d^2, padding
-constexpr int kIcpTerms = 29;
+static_assert(kIcpPts * kIcpWaves == kIcpBlockPts, "one partial row per block");
 constexpr int kIcpStripes = kIcpBlock / kIcpRow;      // 8 row stripes in the update's reduction
 constexpr int64_t kNormalsMaxN = (int64_t)1 << 18;
 constexpr uint64_t kNoKey = ~(uint64_t)0;
@@ -43,11 +41,6 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
   }
   return v;
 }
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
 
 // One tile of the cloud into LDS (x, y, z planes); entries past n are left unread by the callers.
 __device__ __forceinline__ void load_tile(const float* __restrict__ pts, int64_t base, int cnt, float* tx, float* ty,
@@ -59,43 +52,6 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ pts, int64_t
 }
 
 // ------------------------------------------------------------------ normals
-// Jacobi rotation annihilating a_pq of a symmetric 3x3; r is the third index.  (Numerical Recipes' jacobi.)
-__device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
-                                           double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
-  if (apq == 0.0) return;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));  // 0 when theta overflows
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  app -= t * apq;
-  aqq += t * apq;
-  apq = 0.0;
-  double x = arp, y = arq;
-  arp = c * x - s * y, arq = s * x + c * y;
-  x = v0p, y = v0q, v0p = c * x - s * y, v0q = s * x + c * y;
-  x = v1p, y = v1q, v1p = c * x - s * y, v1q = s * x + c * y;
-  x = v2p, y = v2q, v2p = c * x - s * y, v2q = s * x + c * y;
-}
-
-// Unit eigenvector of the smallest eigenvalue of the symmetric matrix (a00 a01 a02; . a11 a12; . . a22).
-__device__ __forceinline__ void smallest_eigvec(double a00, double a01, double a02, double a11, double a12, double a22,
-                                                double& nx, double& ny, double& nz) {
-  double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
-    jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0, 1), r = 2
-    jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0, 2), r = 1
-    jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1, 2), r = 0
-  }
-  // the column of the smallest diagonal entry (ties to the lower index), picked with 0 / 1 weights: selects between
-  // the columns would be turned into an indexed private array
-  const double w1 = (a11 < a00 && !(a22 < a11)) ? 1.0 : 0.0, w2 = (a22 < a00 && a22 < a11) ? 1.0 : 0.0;
-  const double w0 = 1.0 - w1 - w2;
-  const double x = w0 * v00 + w1 * v01 + w2 * v02, y = w0 * v10 + w1 * v11 + w2 * v12,
-               z = w0 * v20 + w1 * v21 + w2 * v22;
-  const double len = sqrt(x * x + y * y + z * z);
-  nx = x / len, ny = y / len, nz = z / len;
-}
-
 __global__ void __launch_bounds__(kIcpBlock)
     k_cloud_normals(const float* __restrict__ pts, int32_t n, int32_t k, float* __restrict__ normals) {
   __shared__ float tx[kIcpTile], ty[kIcpTile], tz[kIcpTile];
@@ -131,20 +87,10 @@ __global__ void __launch_bounds__(kIcpBlock)
   const bool has = lane < k;
   const int64_t id = has ? (int64_t)(uint32_t)list : qc;
   const double px = pts[id * 3], py = pts[id * 3 + 1], pz = pts[id * 3 + 2];
-  const double inv = 1.0 / (double)k;
-  const double mx = wave_sum_f64(has ? px : 0.0) * inv, my = wave_sum_f64(has ? py : 0.0) * inv,
-               mz = wave_sum_f64(has ? pz : 0.0) * inv;
-  const double cx = has ? px - mx : 0.0, cy = has ? py - my : 0.0, cz = has ? pz - mz : 0.0;
-  const double a00 = wave_sum_f64(cx * cx) * inv, a01 = wave_sum_f64(cx * cy) * inv, a02 = wave_sum_f64(cx * cz) * inv,
-               a11 = wave_sum_f64(cy * cy) * inv, a12 = wave_sum_f64(cy * cz) * inv, a22 = wave_sum_f64(cz * cz) * inv;
+  double cov[6];
+  neighbour_covariance(has, px, py, pz, k, cov);
   if (!live || lane != 0) return;
-  double nx = 0.0, ny = 0.0, nz = 1.0;
-  const bool zero = a00 == 0.0 && a01 == 0.0 && a02 == 0.0 && a11 == 0.0 && a12 == 0.0 && a22 == 0.0;
-  if (!zero) smallest_eigvec(a00, a01, a02, a11, a12, a22, nx, ny, nz);
-  if (!(isfinite(nx) && isfinite(ny) && isfinite(nz))) nx = 0.0, ny = 0.0, nz = 1.0;
-  if (nx * (double)qx + ny * (double)qy + nz * (double)qz > 0.0) nx = -nx, ny = -ny, nz = -nz;
-  float* o = normals + q * 3;
-  o[0] = (float)nx, o[1] = (float)ny, o[2] = (float)nz;
+  write_normal(cov, false, qx, qy, qz, normals + q * 3);
 }
 
 // ------------------------------------------------------------------ ICP
@@ -169,12 +115,7 @@ __global__ void __launch_bounds__(kIcpBlock)
 #pragma unroll
   for (int a = 0; a < kIcpPts; ++a) {
     const int64_t i = min(first + a, (int64_t)n_src - 1);  // the tail repeats the last point and is masked below
-    const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      pd[a][r] = T[4 * r] * sx + T[4 * r + 1] * sy + T[4 * r + 2] * sz + T[4 * r + 3];
-      pf[a][r] = (float)pd[a][r];
-    }
+    icp_transform(T, src[i * 3], src[i * 3 + 1], src[i * 3 + 2], pd[a], pf[a]);
     best[a] = INFINITY;
     besti[a] = 0xFFFFFFFFu;
   }
@@ -205,25 +146,12 @@ __global__ void __launch_bounds__(kIcpBlock)
       if (corr_d2) corr_d2[i] = keep ? d2 : 0.f;
     }
     if (!keep) {
-#pragma unroll
-      for (int t = 0; t < kIcpTerms; ++t) row[t] = 0.0;
+      icp_zero_terms(row);
       continue;
     }
     const int64_t c = (int64_t)(uint32_t)key;
-    const double px = pd[a][0], py = pd[a][1], pz = pd[a][2];
-    const double ex = px - (double)tgt[c * 3], ey = py - (double)tgt[c * 3 + 1], ez = pz - (double)tgt[c * 3 + 2];
-    const double nx = tgt_normals[c * 3], ny = tgt_normals[c * 3 + 1], nz = tgt_normals[c * 3 + 2];
-    const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-    const double r = ex * nx + ey * ny + ez * nz;
-    int t = 0;
-#pragma unroll
-    for (int u = 0; u < 6; ++u)
-#pragma unroll
-      for (int v = u; v < 6; ++v) row[t++] = J[u] * J[v];
-#pragma unroll
-    for (int u = 0; u < 6; ++u) row[21 + u] = J[u] * r;
-    row[27] = 1.0;
-    row[28] = ex * ex + ey * ey + ez * ez;
+    icp_pair_terms(pd[a][0], pd[a][1], pd[a][2], tgt[c * 3], tgt[c * 3 + 1], tgt[c * 3 + 2], tgt_normals[c * 3],
+                   tgt_normals[c * 3 + 1], tgt_normals[c * 3 + 2], row);
   }
   __syncthreads();
   if (threadIdx.x < kIcpRow) {
@@ -335,6 +263,12 @@ __global__ void __launch_bounds__(kIcpBlock)
   st->converged = converged ? 1 : 0;
 }
 
+void icp_launch_update(const double* partials, int32_t n_rows, int32_t n_src, int32_t round, int32_t max_iterations,
+                       double rel_fitness, double rel_rmse, lnr_icp_state* state, hipStream_t stream) {
+  hipLaunchKernelGGL(k_icp_update, dim3(1), dim3(kIcpBlock), 0, stream, partials, n_rows, n_src, round, max_iterations,
+                     rel_fitness, rel_rmse, state);
+}
+
 }  // namespace lnr
 
 using namespace lnr;
@@ -386,9 +320,8 @@ extern "C" int lnr_icp_stage(const float* src, int64_t n_src, const float* tgt, 
     hipLaunchKernelGGL(k_icp_correspond, dim3((unsigned)rows), dim3(kIcpBlock), 0, as_stream(stream), src,
                        (int32_t)n_src, tgt, tgt_normals, (int32_t)n_tgt, thr2, round, state,
                        static_cast<double*>(workspace), corr_idx, corr_d2);
-    hipLaunchKernelGGL(k_icp_update, dim3(1), dim3(kIcpBlock), 0, as_stream(stream),
-                       static_cast<const double*>(workspace), (int32_t)rows, (int32_t)n_src, round, max_iterations,
-                       rel_fitness, rel_rmse, state);
+    icp_launch_update(static_cast<const double*>(workspace), (int32_t)rows, (int32_t)n_src, round, max_iterations,
+                      rel_fitness, rel_rmse, state, as_stream(stream));
   }
   LNR_RETURN_LAUNCH("lnr_icp_stage");
 }

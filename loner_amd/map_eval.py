@@ -22,8 +22,9 @@ Deviations from the reference:
   * output order of the voxel filter: ascending cell key (x, then y, then z); Open3D's is that of an unordered map;
   * points are float32 (Open3D holds float64): a voxel's mean is summed in float64 and rounded once, an aligned or
     posed cloud is transformed in float64 and rounded once;
-  * the alignment clouds are capped at ``align_max_points`` = 2^16 points (reference: 10^6), at most 2^17:
-    lnr_cloud_normals stops at 2^18 points and both alignment kernels are O(n^2);
+  * the alignment clouds are capped at ``align_max_points`` = 2^16 points (reference: 10^6) and at most 2^17 with the
+    default exhaustive search, whose two kernels are O(n^2); ``align_search="grid"`` (the same transform bit for bit)
+    takes the reference's 10^6;
   * only the target's normals are estimated: point-to-plane ICP reads no others.
 """
 import os
@@ -37,6 +38,7 @@ from . import _lib as L
 # (tools/map_eval_demo.py, profiles/map_eval_demo.json)
 DEFAULT_CELL_VOXELS = 4
 ALIGN_MAX_POINTS = 1 << 17
+ALIGN_MAX_POINTS_GRID = 1_000_000  # with align_search="grid": the reference's cap
 ALIGN_KNN = 30
 
 
@@ -125,16 +127,22 @@ def statistics(sum_acc, n_acc, false_pos, sum_comp, n_comp, false_neg):
             "f-score": float(2 * (precision * recall) / (precision + recall + 1e-8)), "num_points": int(n_acc)}
 
 
-def _check_align_cap(cap):
-    if not 1 <= int(cap) <= ALIGN_MAX_POINTS:
+def _check_align_cap(cap, search="brute"):
+    if search not in ("brute", "grid"):
+        raise ValueError(f"align_search={search!r} is not one of ('brute', 'grid')")
+    if search == "grid":
+        if not 1 <= int(cap) <= ALIGN_MAX_POINTS_GRID:
+            raise ValueError(f"align_max_points={cap} outside [1, {ALIGN_MAX_POINTS_GRID}] (align_search='grid')")
+    elif not 1 <= int(cap) <= ALIGN_MAX_POINTS:
         raise ValueError(f"align_max_points={cap} outside [1, 2^17]")
 
 
 def compare_point_clouds_ref(est, gt, f_score_threshold=0.1, voxel_size=0.05, align=True, align_max_points=1 << 16,
-                             return_distances=False):
-    """compare_point_clouds in float64 numpy / scipy, on ``tracking.normals_reference`` / ``icp_reference``."""
+                             return_distances=False, align_search="brute"):
+    """compare_point_clouds in float64 numpy / scipy, on ``tracking.normals_reference`` / ``icp_reference``.
+    ``align_search`` only sets the cap ``align_max_points`` is checked against."""
     from . import tracking as TR
-    _check_align_cap(align_max_points)
+    _check_align_cap(align_max_points, align_search)
     e, g = voxel_down_sample_ref(est, voxel_size), voxel_down_sample_ref(gt, voxel_size)
     T = np.eye(4)
     if align:
@@ -341,34 +349,40 @@ def transform_points(points, T):
     return q.float().contiguous()
 
 
-def align_clouds(est, gt, align_max_points=1 << 16):
+def align_clouds(est, gt, align_max_points=1 << 16, search="brute"):
     """The reference's alignment step on filtered device clouds: uniform down-sampling to the cap, normals (k = 30) of
     the target, one point-to-plane ICP stage (0.125 m, 10 iterations, 1e-12 / 1e-12), est onto gt.  Returns T (4, 4)
-    float64 and the stage's state."""
+    float64 and the stage's state.  ``search="grid"``: normals and correspondences on the cell grid
+    (``tracking.cloud_normals_grid``, lnr_icp_stage_grid), the same T bit for bit, with the cap at
+    ALIGN_MAX_POINTS_GRID."""
     from . import tracking as TR
-    _check_align_cap(align_max_points)
+    _check_align_cap(align_max_points, search)
     ae = uniform_down_sample(est, alignment_skip(est.shape[0], align_max_points)).contiguous()
     ag = uniform_down_sample(gt, alignment_skip(gt.shape[0], align_max_points)).contiguous()
     if ag.shape[0] < ALIGN_KNN:
         raise RuntimeError(f"compare_point_clouds: {ag.shape[0]} alignment points are fewer than k={ALIGN_KNN}")
-    T, res = TR.icp(ae, ag, TR.cloud_normals(ag, ALIGN_KNN), [TR.IcpStage(0.125, 10, 1e-12, 1e-12)])
+    normals = TR.cloud_normals_grid(ag, ALIGN_KNN) if search == "grid" else TR.cloud_normals(ag, ALIGN_KNN)
+    T, res = TR.icp(ae, ag, normals, [TR.IcpStage(0.125, 10, 1e-12, 1e-12)], search=search)
+    if res[-1]["status"]:
+        _raise_status(res[-1]["status"], "compare_point_clouds")
     return T, res[-1]
 
 
 def compare_point_clouds(est, gt, f_score_threshold=0.1, voxel_size=0.05, align=True, align_max_points=1 << 16,
-                         cell=None, timer=None, return_distances=False):
+                         cell=None, timer=None, return_distances=False, align_search="brute"):
     """evaluate_lidar_map.compare_point_clouds on float32 (n, 3) device clouds; returns the reference's dict (accuracy,
     completion, chamfer_distance, recall, precision, f-score, num_points).  ``cell``: the search grid's cell, default
-    DEFAULT_CELL_VOXELS x voxel_size.  Both directions' sums and counts come back in one copy."""
+    DEFAULT_CELL_VOXELS x voxel_size.  Both directions' sums and counts come back in one copy.  ``align_search``:
+    ``align_clouds``' search; with "grid" ``align_max_points`` may reach ALIGN_MAX_POINTS_GRID."""
     from .meshing import _NoTimer
     timer = timer or _NoTimer()
-    _check_align_cap(align_max_points)
+    _check_align_cap(align_max_points, align_search)
     with timer("voxel_filter"):
         e, g = voxel_down_sample(est, voxel_size), voxel_down_sample(gt, voxel_size)
     T = np.eye(4)
     if align:
         with timer("align"):
-            T, _ = align_clouds(e, g, align_max_points)
+            T, _ = align_clouds(e, g, align_max_points, align_search)
             e = transform_points(e, T)
     cell = DEFAULT_CELL_VOXELS * float(voxel_size) if cell is None else float(cell)
     with timer("search"):

@@ -2,7 +2,9 @@
 
     frame_point_cloud   Frame.build_point_cloud's index logic (src/common/frame.py:105-146)
     cloud_normals       lnr_cloud_normals: Open3D's estimate_normals() with its default KNN(30)
-    IcpSolver           lnr_icp_init / lnr_icp_stage around a device-resident lnr_icp_state
+    cloud_normals_grid  the same normals from the grid kNN (lnr_knn_search + lnr_normals_from_knn): any cloud size
+    IcpSolver           lnr_icp_init / lnr_icp_stage around a device-resident lnr_icp_state; ``search="grid"`` runs
+                        lnr_icp_stage_grid on a ``GridTarget`` instead (the same states, bit for bit)
     Tracker             track(scan): cloud, normals, the ICP schedule against the previous frame, pose chaining,
                         motion compensation and sky rays (``loner_amd.preprocess``)
     normals_reference, icp_reference
@@ -20,9 +22,25 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import lidar_map as LM
+from . import map_eval as ME
 from . import preprocess as PP
 
 N_SUMS = 27  # J^T J upper triangle (21, row-major) + J^T r (6)
+SEARCHES = ("brute", "grid")
+# A grid stage's cell is max(ICP_CELL_FACTOR x map_eval.default_cell, threshold (1 + 2^-10) / LNR_NN_MAX_RINGS).
+# 0.5 is the fastest of ICP_CELL_FACTORS for the default schedule at 5e3, 3.5e4 and 1e5 points a side, builds included
+# (tools/registration_bench.py, profiles/registration_grid.json, DESIGN.md 7e: 26.8, 29.9, 50.2, 131, 299 ms at 1e5).
+# A scan is far denser near the sensor than default_cell's two points per cell assumes, and one thread walks a cell.
+ICP_CELL_FACTOR = 0.5
+ICP_CELL_FACTORS = (0.5, 1.0, 2.0, 4.0, 8.0)
+NORMALS_CHUNK = 1 << 18  # queries per lnr_knn_search call of cloud_normals_grid: bounds the (n, k) temporaries
+
+
+def check_search(search, what="search"):
+    if search not in SEARCHES:
+        raise ValueError(f"{what}={search!r} is not one of {SEARCHES}")
+    return search
 
 
 # ---------------------------------------------------------------------------------------------- settings
@@ -48,8 +66,10 @@ class TrackerSettings:
     knn: int = 30
     motion_compensation: bool = True
     compute_sky_rays: bool = False
+    search: str = "brute"  # "grid": normals and correspondences on the cell grid (the same results; any cloud size)
 
     def __post_init__(self):
+        check_search(self.search, "tracker search")
         if self.downsample_type == "VOXEL":
             raise NotImplementedError("tracker downsample type VOXEL is not built; use UNIFORM or None")
         if self.downsample_type not in (None, "UNIFORM"):
@@ -217,60 +237,165 @@ def cloud_normals(points, k=30, out=None):
     return out
 
 
+def cloud_normals_grid(points, k=30, cell=None, out=None):
+    """``cloud_normals`` for a cloud of any size up to LNR_CLOUD_MAX_POINTS: the exact k nearest neighbours from the
+    grid search (``lidar_map.knn``), then lnr_normals_from_knn.  The lists are those lnr_cloud_normals finds, so the
+    normals are its normals bit for bit, whatever ``cell`` is (default: ``lidar_map.default_knn_cell``, one read of
+    the cloud's box).  Queries run NORMALS_CHUNK at a time.  The search's status word is read once at the end (a
+    synchronisation): a nan or inf coordinate raises RuntimeError, as the box read does with ``cell=None``."""
+    pts = ME._cloud(points, "cloud_normals_grid")
+    n, k = pts.shape[0], int(k)
+    if not 3 <= k <= min(64, n):
+        raise ValueError(f"cloud_normals_grid: k={k} outside [3, min(64, {n} points)]")
+    if out is None:
+        out = torch.empty_like(pts)
+    grid = LM.knn_grid(pts, k, cell)
+    s = L.stream(pts.device)
+    for a in range(0, n, NORMALS_CHUNK):
+        q = pts[a:a + NORMALS_CHUNK]
+        idx = LM.knn(q, grid, k, check=False)[0]
+        L.call("lnr_normals_from_knn", q, q.shape[0], pts, n, idx, k, out[a:a + NORMALS_CHUNK], s)
+    ME._raise_status(int(grid.status.item()), "cloud_normals_grid")
+    return out
+
+
+def icp_grid_rings_ref(threshold, cell):
+    """lnr_icp_grid_rings in Python: the smallest R in 1 .. LNR_NN_MAX_RINGS with (R cell)^2 (1 - 2^-20) >= thr2, thr2
+    the float32 square of the float32 threshold; 0 if there is none or an argument is out of range."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        thr, cell = np.float32(threshold), float(cell)
+        if not (np.isfinite(thr) and thr > 0 and np.isfinite(cell) and cell >= 1e-12):
+            return 0
+        thr2 = float(np.float32(float(thr) * float(thr)))
+    if not np.isfinite(thr2):
+        return 0
+    for r in range(1, L.NN_MAX_RINGS + 1):
+        bound = float(r) * cell
+        if bound * bound * (1.0 - 2.0 ** -20) >= thr2:
+            return r
+    return 0
+
+
+def icp_grid_cell(threshold, lo, hi, n, factor=None):
+    """The cell of a grid stage: ``factor`` (default ICP_CELL_FACTOR) x ``map_eval.default_cell`` of the target's box,
+    and never so small that the threshold would need more than LNR_NN_MAX_RINGS rings."""
+    factor = ICP_CELL_FACTOR if factor is None else float(factor)
+    floor = float(np.float32(threshold)) * (1.0 + 2.0 ** -10) / L.NN_MAX_RINGS
+    return max(factor * ME.default_cell(lo, hi, n), floor)
+
+
+class GridTarget:
+    """An ICP target for ``search="grid"``: the cloud, its normals, and one ``map_eval.NearestGrid`` per distinct cell,
+    each built when a stage first asks for it.  The cloud's box is read back once (a synchronisation)."""
+
+    def __init__(self, tgt, normals):
+        self.points = ME._cloud(tgt, "GridTarget")
+        self.normals = ME._cloud(normals, "GridTarget normals")
+        if self.normals.shape != self.points.shape:
+            raise ValueError("GridTarget: one normal per point")
+        self.n = self.points.shape[0]
+        self._box = None
+        self._grids = {}
+
+    @property
+    def box(self):
+        if self._box is None:
+            box = torch.stack((self.points.min(dim=0).values, self.points.max(dim=0).values)).tolist()
+            if not np.isfinite(box).all():
+                raise RuntimeError("GridTarget: a coordinate is nan or inf")
+            self._box = box
+        return self._box
+
+    def cell_for(self, threshold, factor=None):
+        return icp_grid_cell(threshold, self.box[0], self.box[1], self.n, factor)
+
+    def grid(self, cell):
+        cell = float(cell)
+        if cell not in self._grids:
+            self._grids[cell] = ME.NearestGrid(self.points, cell)
+        return self._grids[cell]
+
+
 STATE_BYTES = ctypes.sizeof(L.IcpState)
 
 
-def _state_dict(raw):
+def _state_dict(raw, status=0):
     s = L.IcpState.from_buffer_copy(bytes(raw))
-    return dict(T=np.array(s.T, np.float64).reshape(4, 4), fitness=float(s.fitness), rmse=float(s.rmse),
+    return dict(status=int(status), T=np.array(s.T, np.float64).reshape(4, 4), fitness=float(s.fitness), rmse=float(s.rmse),
                 sum_d2=float(s.sum_d2), sums=np.array(s.sums, np.float64), n_corr=int(s.n_corr),
                 iterations=int(s.iterations), converged=bool(s.converged))
 
 
 class IcpSolver:
     """The ICP schedule on one device: state, per-stage snapshots and the workspace are allocated once (the workspace
-    grows with the largest source cloud seen).  ``run`` only enqueues; ``read`` is the one synchronisation."""
+    grows with the largest source cloud seen).  ``run`` only enqueues; ``read`` is the one synchronisation (with
+    ``search="grid"`` a target given as a tensor is wrapped in a ``GridTarget``, whose box is one more read).  The
+    status word (LNR_CLOUD_NONFINITE, LNR_CLOUD_GRID_RANGE; grid stages only) is cleared by ``init`` and snapshot with
+    every stage."""
 
     def __init__(self, device, max_stages=4):
         self.device = torch.device(device)
         self.state = torch.zeros(STATE_BYTES, dtype=torch.uint8, device=self.device)
         self.snap = torch.zeros(max_stages, STATE_BYTES, dtype=torch.uint8, device=self.device)
         self.ws = torch.empty(0, dtype=torch.float64, device=self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.status_snap = torch.zeros(max_stages, dtype=torch.int32, device=self.device)
         self.n_stages = 0
 
     def init(self, T0=None):
         T = np.eye(4) if T0 is None else np.asarray(T0, np.float64)
         arr = (ctypes.c_double * 16)(*T.reshape(-1).tolist())
         L.call("lnr_icp_init", self.state, arr, L.stream(self.device))
+        self.status.zero_()
         self.n_stages = 0
 
-    def stage(self, src, tgt, tgt_normals, st, corr_idx=None, corr_d2=None):
-        need = int(L.lib().lnr_icp_workspace_bytes(src.shape[0]))
+    def stage(self, src, tgt, tgt_normals, st, corr_idx=None, corr_d2=None, search="brute", cell=None):
+        """One stage from the state's T.  ``search="grid"``: ``tgt`` is a ``GridTarget`` (``tgt_normals`` is then
+        ignored) or a cloud that is wrapped in one; ``cell`` overrides ``GridTarget.cell_for(threshold)``."""
+        check_search(search)
+        grid = search == "grid"
+        need = int((L.lib().lnr_icp_grid_workspace_bytes if grid else L.lib().lnr_icp_workspace_bytes)(src.shape[0]))
         if self.ws.numel() * 8 < need:
             self.ws = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        L.call("lnr_icp_stage", src, src.shape[0], tgt, tgt_normals, tgt.shape[0], float(st.threshold),
-               int(st.max_iterations), float(st.relative_fitness), float(st.relative_rmse), self.state, self.ws,
-               self.ws.numel() * 8, corr_idx, corr_d2, L.stream(self.device))
+        crit = (float(st.threshold), int(st.max_iterations), float(st.relative_fitness), float(st.relative_rmse))
+        if grid:
+            gt = tgt if isinstance(tgt, GridTarget) else GridTarget(tgt, tgt_normals)
+            g = gt.grid(gt.cell_for(st.threshold) if cell is None else cell)
+            L.call("lnr_icp_stage_grid", src, src.shape[0], g.points, g.keys, g.perm, g.n, g.origin, g.cell, g.dims,
+                   gt.normals, *crit, self.state, self.ws, self.ws.numel() * 8, corr_idx, corr_d2, self.status,
+                   L.stream(self.device))
+            self.status |= g.status  # what the target's own keys reported
+        else:
+            L.call("lnr_icp_stage", src, src.shape[0], tgt, tgt_normals, tgt.shape[0], *crit, self.state, self.ws,
+                   self.ws.numel() * 8, corr_idx, corr_d2, L.stream(self.device))
         if self.n_stages >= self.snap.shape[0]:
             self.snap = torch.cat([self.snap, torch.zeros_like(self.snap)])
+            self.status_snap = torch.cat([self.status_snap, torch.zeros_like(self.status_snap)])
         self.snap[self.n_stages].copy_(self.state)
+        self.status_snap[self.n_stages:self.n_stages + 1].copy_(self.status)
         self.n_stages += 1
 
-    def run(self, src, tgt, tgt_normals, schedule, T0=None):
+    def run(self, src, tgt, tgt_normals, schedule, T0=None, search="brute"):
         self.init(T0)
+        if check_search(search) == "grid" and not isinstance(tgt, GridTarget):
+            tgt = GridTarget(tgt, tgt_normals)  # one box, one grid per distinct cell for the whole schedule
         for st in schedule:
-            self.stage(src, tgt, tgt_normals, st)
+            self.stage(src, tgt, tgt_normals, st, search=search)
 
     def read(self):
-        """The state after each stage run since ``init`` (one device-to-host copy)."""
-        raw = self.snap[:self.n_stages].cpu().numpy()
-        return [_state_dict(r) for r in raw]
+        """The state after each stage run since ``init``, with the status word as it stood then (one device-to-host
+        copy)."""
+        n = self.n_stages
+        raw = torch.cat([self.snap[:n].reshape(-1), self.status_snap[:n].view(torch.uint8)]).cpu().numpy()
+        status = raw[n * STATE_BYTES:].view(np.int32)
+        return [_state_dict(raw[i * STATE_BYTES:(i + 1) * STATE_BYTES], status[i]) for i in range(n)]
 
 
-def icp(src, tgt, tgt_normals, schedule, T0=None, solver=None):
-    """Run ``schedule`` on device clouds; returns (T (4, 4) float64, per-stage state dicts)."""
+def icp(src, tgt, tgt_normals, schedule, T0=None, solver=None, search="brute"):
+    """Run ``schedule`` on device clouds; returns (T (4, 4) float64, per-stage state dicts).  ``search``: "brute"
+    (lnr_icp_stage) or "grid" (lnr_icp_stage_grid; ``tgt`` may be a ``GridTarget``): the same states bit for bit."""
     solver = solver or IcpSolver(src.device)
-    solver.run(src, tgt, tgt_normals, schedule, T0)
+    solver.run(src, tgt, tgt_normals, schedule, T0, search=search)
     res = solver.read()
     return (res[-1]["T"] if res else (np.eye(4) if T0 is None else np.asarray(T0, np.float64))), res
 
@@ -282,7 +407,7 @@ class Tracker:
         self.settings = settings or TrackerSettings()
         self.device = torch.device(device)
         self._solver = IcpSolver(self.device, max_stages=max(1, len(self.settings.schedule)))
-        self._ref_points = None
+        self._ref_points = None  # with search="grid": a GridTarget
         self._ref_normals = None
         self._ref_pose = np.eye(4) if initial_pose is None else PP._np(initial_pose).copy()
         self._ref_time = None
@@ -317,12 +442,13 @@ class Tracker:
         pts, dirs, dist = self._cloud(scan)
         if pts.shape[0] < s.knn:
             raise RuntimeError(f"Tracker: a cloud of {pts.shape[0]} points is smaller than knn={s.knn}")
-        normals = cloud_normals(pts, s.knn)
+        grid = s.search == "grid"
+        normals = cloud_normals_grid(pts, s.knn) if grid else cloud_normals(pts, s.knn)
         if self._ref_points is None:
             pose = self._ref_pose.copy()
             res = []
         else:
-            T, res = icp(pts, self._ref_points, self._ref_normals, s.schedule, solver=self._solver)
+            T, res = icp(pts, self._ref_points, self._ref_normals, s.schedule, solver=self._solver, search=s.search)
             pose = self._ref_pose @ T
             if s.motion_compensation and ts is not None:
                 dp3 = dirs.t().contiguous()
@@ -334,7 +460,7 @@ class Tracker:
         if s.compute_sky_rays:
             d = scan["directions"].to(self.device, torch.float32)
             scan["sky_directions"] = PP.sky_rays(d.t().contiguous(), pose).t()
-        self._ref_points, self._ref_normals = pts, normals
+        self._ref_points, self._ref_normals = (GridTarget(pts, normals) if grid else pts), normals
         self._ref_pose, self._ref_time = pose, float(time)
         self.frame_count += 1
         last = res[-1] if res else None

@@ -10,6 +10,7 @@ both directions, HIP events, the median of five runs after a warm-up:
 
     python tools/map_eval_demo.py [--steps 300] [--skip-step 5] [--resolution 0.25] [--voxel 0.1]
                                   [--json profiles/map_eval_demo.json] [--pcd map.pcd]
+                                  [--align-search grid --align-max-points 1000000]
 """
 import argparse
 import json
@@ -108,6 +109,9 @@ def main():
     ap.add_argument("--pcd", default=None)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "map_eval_demo.json"))
     ap.add_argument("--no-search-benchmark", action="store_true")
+    ap.add_argument("--align-search", default="brute", choices=("brute", "grid"),
+                    help="the alignment's search; grid lifts the cap on the alignment clouds to 10^6 points")
+    ap.add_argument("--align-max-points", type=int, default=1 << 16)
     args = ap.parse_args()
     import bench
     from loner_amd import map_eval as ME
@@ -142,8 +146,10 @@ def main():
                rendered_points=int(est.shape[0]), ground_truth_points=int(gt.shape[0]))
     if args.pcd:
         ME.write_pcd(args.pcd, est)
-    ME.compare_point_clouds(est, gt, args.f_score_threshold, args.voxel)  # warm-up
-    stats = ME.compare_point_clouds(est, gt, args.f_score_threshold, args.voxel, timer=timer)
+    align = dict(align_search=args.align_search, align_max_points=args.align_max_points)
+    rec.update(align)
+    ME.compare_point_clouds(est, gt, args.f_score_threshold, args.voxel, **align)  # warm-up
+    stats = ME.compare_point_clouds(est, gt, args.f_score_threshold, args.voxel, timer=timer, **align)
     rec["statistics"] = stats
     rec["stage_ms"] = {k: round(v, 4) for k, v in timer.times_ms().items()}
     rec["voxel_filter_gt"] = dict(points=int(gt.shape[0]), voxel_m=args.voxel,

@@ -4,6 +4,11 @@ normals kernel and of the two-stage ICP schedule, and beside them the wall time 
 restatement (normals_reference, icp_schedule_reference) on the same clouds.
 
     python tools/track_demo.py [--kind quad] [--scans 8] [--points 5000] [--json out.json]
+                               [--search grid] [--full-scans]
+
+--search grid runs normals and correspondences on the cell grid (the same poses, bit for bit); --full-scans tracks
+without decimation (the reference's ``downsample.type: None``), which wants --search grid: the exhaustive kernels
+are O(n^2).  With --full-scans the float64 restatement is skipped above 20 000 points (its k-d trees take seconds).
 """
 import argparse
 import json
@@ -56,6 +61,8 @@ def main():
     ap.add_argument("--scans", type=int, default=8)
     ap.add_argument("--points", type=int, default=5000)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--search", default="brute", choices=("brute", "grid"))
+    ap.add_argument("--full-scans", action="store_true", help="no decimation (downsample type None)")
     args = ap.parse_args()
     from loner_amd import synthetic as syn
     from loner_amd import tracking as TR
@@ -64,7 +71,10 @@ def main():
     for i in range(args.scans - 1):
         poses.append(poses[-1] @ step_pose(i))
     win = syn.make_window(args.kind, args.scans, seed=3, poses=poses)
-    settings = TR.TrackerSettings(target_uniform_point_count=args.points)
+    target = None if args.full_scans else args.points
+    settings = TR.TrackerSettings(target_uniform_point_count=args.points, search=args.search,
+                                  downsample_type=None if args.full_scans else "UNIFORM")
+    normals = TR.cloud_normals_grid if args.search == "grid" else TR.cloud_normals
     tracker = TR.Tracker(settings, dev)
     solver = TR.IcpSolver(dev)
     frames, ref_pose, prev, prev_dev = [], np.eye(4), None, None
@@ -76,12 +86,15 @@ def main():
         torch.cuda.synchronize()
         wall_gpu = time.perf_counter() - t0
         # the same cloud through the float64 restatement
-        pts = TR.frame_point_cloud(w["directions"], w["distances"], target_points=args.points)
+        pts = TR.frame_point_cloud(w["directions"], w["distances"], target_points=target)
+        with_ref = pts.shape[0] <= 20000
         t0 = time.perf_counter()
-        nrm = TR.normals_reference(pts.numpy(), settings.knn)
+        nrm = TR.normals_reference(pts.numpy(), settings.knn) if with_ref else None
         t_nrm = time.perf_counter() - t0
         t_icp, ref_it = 0.0, []
-        if prev is not None:
+        if not with_ref:
+            ref_pose = out["pose"]  # no restatement at this size: its columns repeat the GPU's
+        elif prev is not None:
             t0 = time.perf_counter()
             T, res = TR.icp_schedule_reference(pts.numpy(), prev[0], prev[1], settings.schedule)
             t_icp = time.perf_counter() - t0
@@ -90,10 +103,10 @@ def main():
         # the kernels alone, event-timed
         pd = pts.to(dev)
         nd = torch.empty_like(pd)
-        ms_nrm = event_ms(lambda: TR.cloud_normals(pd, settings.knn, nd))
+        ms_nrm = event_ms(lambda: normals(pd, settings.knn, out=nd))
         ms_icp = 0.0
-        if prev_dev is not None:
-            ms_icp = event_ms(lambda: solver.run(pd, prev_dev[0], prev_dev[1], settings.schedule))
+        if prev_dev is not None:  # with the grid search the target's grids are built inside the timed run
+            ms_icp = event_ms(lambda: solver.run(pd, prev_dev[0], prev_dev[1], settings.schedule, search=args.search))
         et, er = pose_error(out["pose"], truth)
         rt, rr = pose_error(ref_pose, truth)
         dt, dr = pose_error(out["pose"], ref_pose)
@@ -109,7 +122,7 @@ def main():
               f"{t_nrm * 1e3:.1f} ms, schedule {t_icp * 1e3:.1f} ms)", flush=True)
         prev, prev_dev = (pts.numpy(), nrm), (pd, nd)
     tracked = frames[1:]
-    rec = dict(kind=args.kind, scans=args.scans, target_points=args.points,
+    rec = dict(kind=args.kind, scans=args.scans, target_points=target, search=args.search,
                path_length_m=float(sum(np.linalg.norm(step_pose(i)[:3, 3]) for i in range(args.scans - 1))),
                final_drift_mm=frames[-1]["err_mm"], final_drift_deg=frames[-1]["err_deg"],
                reference_final_drift_mm=frames[-1]["reference_err_mm"],
